@@ -14,8 +14,12 @@ ya_vo_amd.sharding.FrameShard), so no image stage communicates.  The only
 collective is the shared map's: every step the ranks all-gather their map blocks (RCCL over xGMI) on a
 communication stream and place them in world coordinates, overlapped with the next step's image kernels.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`).  Everything else
+the benchmark measures or checks -- the per-stage event pass and rooflines, the upload / end-to-end / PNG / sequence /
+LoopHandler legs, the CPU baselines and the pose check -- runs only with --full.
 """
 import argparse
 import json
@@ -65,6 +69,15 @@ def parse():
     ap.add_argument("--frames", type=int, default=2048,
                     help="stereo frames per step per GPU (2048: eight pose-LM problems per CU, four rounds; r03 measured "
                          "214k / 219k / 221k frames/s at 1024 / 1536 / 2048 on one box, profiles/r03/c51)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg and check (per-stage events and rooflines, "
+                         "upload / end-to-end / PNG / sequence / LoopHandler legs, CPU baselines, pose check); the "
+                         "options below that size those legs take effect only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed (rank 0's shard) as "
+                         "DIR/<name>.npy, float32 / float64: every frame's pose and the per-image / per-pair counts, "
+                         "and the keypoints, descriptors, matches and PnP edges of a fixed seeded sample of images, "
+                         "pairs and tracks, the placed shared map's keyframes and landmarks")
     ap.add_argument("--cpu-baseline", choices=["both", "literal", "efficient", "none"], default="both")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="host threads of the CPU baseline (0: the usable cores, affinity capped by OMP_NUM_THREADS)")
@@ -140,6 +153,86 @@ def stage_valu_ops(counts, n_img):
     # separable blur, 9 + 9 MACs per pixel
     # matcher (VALU formulation): Kq * Kt * (8 xor + 8 bcnt-accumulate + 2 min) = 18 per pair
     return {"detect": n_img * (36.0e6 + 18.0 * H * W), "match": float(np.sum(kq * kt)) * 18.0}
+
+
+DUMP_SAMPLE = 32  # images / pairs / tracks whose full records --dump-outputs writes
+DUMP_MAX_LANDMARKS = 1 << 20  # 32 MB of float64 rows; more are cut to a seeded sample
+
+
+def dump_outputs(out_dir, ctx, shard, use_map):
+    """--dump-outputs: what the last step left for its caller, as out_dir/<name>.npy (float32 / float64, < 64 MB).
+
+    Whole: the step's relative poses, the per-image keypoint counts, the per-pair match counts (all / kept by
+    removeOutliers) and the per-track PnP edge and LM-inlier counts; the placed shared map's keyframes (frame id,
+    T_wc) and landmarks (id, X).  Sampled (DUMP_SAMPLE indices drawn once from a fixed seed, stored beside the
+    records): per image the keypoints (row, col, the 32 descriptor bytes), per pair the matches and the kept
+    matches (query row, col, train row, col, distance), per track the PnP edges (X, uv, the LM's outlier flag).
+    Records past an item's count are zero.  Call after drain()."""
+    import ya_vo_amd as yv
+    from ya_vo_amd import map as ymap
+    os.makedirs(out_dir, exist_ok=True)
+    v = shard.batch.view()
+    kp_cap, n_img, n_pairs, nt = shard.max_kp, shard.n_images, len(shard.pairs), shard.n_tracks
+
+    def save(name, a, dtype=np.float64):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=dtype))
+
+    def sample(n, salt):
+        return np.sort(np.random.default_rng(20240 + salt).choice(n, min(DUMP_SAMPLE, n), replace=False))
+
+    kpc, mc, fc, ec = (np.clip(ctx.download(p, np.int32, n), 0, kp_cap) for p, n in (
+        (v.kp_count, n_img), (v.match_count, n_pairs), (v.filt_count, n_pairs), (v.edge_count, nt)))
+    save("poses", shard.poses())
+    save("keypoint_count", kpc)
+    save("match_count", mc)
+    save("filtered_count", fc)
+    save("edge_count", ec)
+    save("track_inliers", ctx.download(v.track_inliers, np.int32, nt))
+
+    imgs = sample(n_img, 0)
+    kps = np.zeros((len(imgs), kp_cap, 34), np.float32)
+    for s, i in enumerate(imgs):
+        if not kpc[i]:
+            continue
+        k = ctx.download(v.keypoints + int(i) * kp_cap * 48, yv.KEYPOINT_DTYPE, int(kpc[i]))
+        kps[s, :len(k), 0], kps[s, :len(k), 1], kps[s, :len(k), 2:] = k["x"], k["y"], k["featVec"]
+    save("sample_images", imgs)
+    save("keypoints", kps, np.float32)
+
+    prs = sample(n_pairs, 1)
+    for name, base, cnt in (("matches", v.matches, mc), ("filtered", v.filtered, fc)):
+        rec = np.zeros((len(prs), kp_cap, 5), np.float32)
+        for s, p in enumerate(prs):
+            if not cnt[p]:
+                continue
+            m = ctx.download(base + int(p) * kp_cap * 100, yv.MATCH_DTYPE, int(cnt[p]))
+            rec[s, :len(m)] = np.stack([m["pt1"]["x"], m["pt1"]["y"], m["pt2"]["x"], m["pt2"]["y"], m["distance"]], 1)
+        save(name, rec, np.float32)
+    save("sample_pairs", prs)
+
+    trs = sample(nt, 2)
+    edges = np.zeros((len(trs), kp_cap, 6), np.float64)
+    for s, t in enumerate(trs):
+        n, base = int(ec[t]), int(t) * kp_cap
+        if not n:
+            continue
+        edges[s, :n, 0:3] = ctx.download(v.edge_X + base * 24, np.float64, n * 3).reshape(n, 3)
+        edges[s, :n, 3:5] = ctx.download(v.edge_uv + base * 16, np.float64, n * 2).reshape(n, 2)
+        edges[s, :n, 5] = ctx.download(v.edge_outlier + base, np.uint8, n)
+    save("sample_tracks", trs)
+    save("edges", edges)
+
+    if use_map:
+        kf_rows, lm_rows = [], []
+        for raw in shard.placed_map():
+            _, kfs, lms = ymap.parse_block(raw)
+            kf_rows.append(np.column_stack([kfs["frame_id"].astype(np.float64), kfs["T"]]).reshape(-1, 8))
+            lm_rows += [np.column_stack([lm["id"].astype(np.float64), lm["X"]]).reshape(-1, 4) for lm in lms]
+        lm_all = np.concatenate(lm_rows) if lm_rows else np.zeros((0, 4))
+        if len(lm_all) > DUMP_MAX_LANDMARKS:
+            lm_all = lm_all[np.sort(np.random.default_rng(20243).choice(len(lm_all), DUMP_MAX_LANDMARKS, replace=False))]
+        save("map_keyframes", np.concatenate(kf_rows))
+        save("map_landmarks", lm_all)
 
 
 def write_png_sequence(base, left, right, threads):
@@ -473,6 +566,11 @@ def spawn_ranks(plans, argv, script=None):
 
 def main():
     args = parse()
+    if not args.full:
+        # a plain run is the headline alone: no events in or after the timed region, no further leg, no CPU work
+        args.no_timing = True
+        args.e2e_steps = args.png_steps = args.sequence_frames = args.loop_handler_frames = 0
+        args.cpu_baseline = "none"
     backend = os.environ.get("YAVO_BENCH_BACKEND", "nccl")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `bench.py --gpus N` without torchrun: one fresh process per GPU, started before this process touches the GPU
@@ -569,17 +667,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, shard, use_map)
+
     # PCIe-inclusive rate: the same step's frames uploaded from pinned host memory, timed alone;
     # reported beside `value` (which has the inputs resident in HBM), never as it
-    h_frames = torch.from_numpy(images).pin_memory()
-    d_up = torch.empty_like(d_frames)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(3):
-        d_up.copy_(h_frames, non_blocking=True)
-    torch.cuda.synchronize()
-    h2d_ms = (time.perf_counter() - t1) / 3 * 1e3
-    del d_up, h_frames
+    h2d_ms = None
+    if args.full:
+        h_frames = torch.from_numpy(images).pin_memory()
+        d_up = torch.empty_like(d_frames)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(3):
+            d_up.copy_(h_frames, non_blocking=True)
+        torch.cuda.synchronize()
+        h2d_ms = (time.perf_counter() - t1) / 3 * 1e3
+        del d_up, h_frames
 
     # end-to-end rate: every step's frames go host -> HBM from pinned memory into one of two device
     # buffers on a copy stream while the previous step's kernels run.  The upload of step i + 1 waits only for the
@@ -820,8 +923,10 @@ def main():
         f"detect: HIP events over the timed region ({args.steps} steps); the other stages: a separate "
         f"{args.stage_steps}-step pass after it with events around every stage",
         "stage_rooflines": per_stage if not args.no_timing else None,
-        "h2d_upload_ms_per_step": round(h2d_ms, 4),
-        "pcie_inclusive_frames_per_s": round(frames_total / (elapsed + args.steps * h2d_ms / 1e3), 2),
+        "full": args.full,
+        "h2d_upload_ms_per_step": None if h2d_ms is None else round(h2d_ms, 4),
+        "pcie_inclusive_frames_per_s": None if h2d_ms is None else
+        round(frames_total / (elapsed + args.steps * h2d_ms / 1e3), 2),
         "end_to_end": e2e,
         "png_end_to_end": png_e2e,
         "loop_handler": lh,

@@ -54,11 +54,13 @@ def _stub(tmp_path, body):
 
 def test_spawn_passes_rank0_stdout_and_waits_for_all(tmp_path, capfd):
     script = _stub(tmp_path, """
-        import json, os
+        import json, os, sys
         if os.environ["RANK"] == "0":
             print(json.dumps({"world": int(os.environ["WORLD_SIZE"])}))
         else:
-            print("rank", os.environ["RANK"])  # goes to stderr via the parent
+            # goes to stderr via the parent; one write per line, so that two ranks sharing that stream cannot
+            # interleave their words when Python runs unbuffered (print writes its arguments piece by piece)
+            sys.stdout.write("rank " + os.environ["RANK"] + "\\n")
     """)
     plans = bench.launch_plan(3, dict(os.environ, YAVO_X="1"), 3, "nccl")
     assert bench.spawn_ranks(plans, [], script=script) == 0
@@ -102,14 +104,17 @@ def test_exchange_summary_reports_hidden_and_exposed_gathers():
 
 def test_bench_reports_world_size_and_collective_timing():
     """The bench line carries world_size_seen and the collective timing beside the shared map,
-    and the configs[2] sequence leg is on by default."""
+    and the configs[2] sequence leg is on by default in a --full run (a plain run times the headline steps only)."""
     src = open(os.path.join(ROOT, "bench.py")).read()
     assert '"world_size_seen": dist.get_world_size() if dist.is_initialized() else 1' in src
     assert '"collective_timing": coll_stats' in src
     sys_argv = sys.argv
     try:
         sys.argv = ["bench.py"]
+        plain = bench.parse()
+        sys.argv = ["bench.py", "--full"]
         a = bench.parse()
     finally:
         sys.argv = sys_argv
-    assert a.sequence_frames == 1000 and a.sequence_cpu == 1  # timed over 1000, the first 200 checked
+    assert not plain.full and plain.dump_outputs is None
+    assert a.full and a.sequence_frames == 1000 and a.sequence_cpu == 1  # timed over 1000, the first 200 checked

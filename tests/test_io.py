@@ -72,22 +72,22 @@ def _gray_from_rgb(r, g, b):
     return np.where((r == g) & (r == b), r, v).astype(np.uint8)
 
 
-REF_EPILINES = "/root/reference/tests/epilines.png"  # the full KITTI frame (CC BY-NC-SA): read in place, not copied
+# the reference's tests/epilines.png, a full KITTI frame (KITTI odometry data, CC BY-NC-SA 3.0), stored as a fixture
+REF_EPILINES = os.path.join(GOLDEN, "png", "epilines.png")
 
 
 @pytest.mark.parametrize("name", ["epilines_crop.png", "testBresenham.png"])
 def test_reference_pngs_match_pil(name):
     """testBresenham.png is the reference's own fixture; epilines_crop.png is a 256 x 128 crop of its KITTI frame
-    (tests/epilines.png) re-encoded by PIL with adaptive filters (only crops are committed)."""
+    (tests/epilines.png) re-encoded by PIL with adaptive filters."""
     path = os.path.join(GOLDEN, "png", name)
     got = yio.imread_gray(path)
     ref = np.array(Image.open(path).convert("L"))  # grey / black-and-white: every grey rule agrees
     np.testing.assert_array_equal(got, ref)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_EPILINES), reason="the reference checkout is not on this host")
 def test_reference_kitti_png_matches_pil_and_crops():
-    """The reference's own KITTI frame, decoded where it lies (the build container holds the reference)."""
+    """The reference's own KITTI frame (as OpenCV wrote it), decoded whole and compared with PIL and the crops."""
     got = yio.imread_gray(REF_EPILINES)
     np.testing.assert_array_equal(got, np.array(Image.open(REF_EPILINES).convert("L")))
     np.testing.assert_array_equal(got[100:228, 400:656], yio.imread_gray(os.path.join(GOLDEN, "png",

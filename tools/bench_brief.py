@@ -9,7 +9,7 @@ for f in sys.argv[1:]:
         print(f, "no JSON line")
         continue
     d = json.loads(lines[-1])
-    st = d.get("stages_ms_per_launch", {})
-    m = d.get("stage_rooflines", {}).get("match", {})
+    st = d.get("stages_ms_per_launch") or {}  # empty / null unless the log is a `bench.py --full` run
+    m = (d.get("stage_rooflines") or {}).get("match", {})
     print(f"{f}: {d['value']:.0f} fps {d['ms_per_step']:.3f} ms | " + " ".join(f"{k} {v:.3f}" for k, v in st.items())
           + (f" | match frac {m.get('frac')}" if m else ""))

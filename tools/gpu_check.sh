@@ -25,10 +25,10 @@ if [ "${SKIP_TESTS:-0}" != "1" ]; then
     run pytest_gpu 900 python -u -m pytest tests -m gpu -v -rf --timeout 120 --timeout-method thread; st=$?; ok $st || exit $st
     run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; st=$?; ok $st || exit $st
 fi
-run bench 900 python bench.py "$@"; st=$?; ok $st || exit $st
+run bench 900 python bench.py --full "$@"; st=$?; ok $st || exit $st
 [ "${PROFILE:-1}" = "1" ] || exit 0
 export TMPDIR=/tmp
 run rocprof 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o bench -- \
-    python3 "$ROOT/bench.py" --cpu-baseline none "$@"; st=$?; ok $st || exit $st
+    python3 "$ROOT/bench.py" --full --cpu-baseline none "$@"; st=$?; ok $st || exit $st
 find "$OUT/prof" -name "*stats*" | head
 exit 0
