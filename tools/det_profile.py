@@ -1,6 +1,6 @@
 """Phase breakdown of detect_kernel (lane 0 of each workgroup, shader-clock cycles) from the profiling build.
 
-    make -C ya_vo_amd/csrc prof && python tools/det_profile.py [--frames 256]"""
+    make -C ya_vo_amd/csrc prof && python tools/det_profile.py [--frames 256] [--lib PATH]"""
 import argparse
 import ctypes
 import os
@@ -15,15 +15,19 @@ import torch  # noqa: E402
 import ya_vo_amd as yv  # noqa: E402
 from ya_vo_amd.synth import synth_stereo_batch  # noqa: E402
 
+# taps <= 127 (the default): both blur passes run on the matrix cores in one phase and the kernel ends after Harris;
+# the last phase is the v_dot2 vertical pass of the fallback path (a tap above 127), whose phase 3 is its horizontal pass
 PHASES = ["stage tile (loads + LDS)", "FAST phase 1 (pretest)", "FAST phase 2 (full test)",
-          "blur horizontal (+ atomic)", "Harris", "blur vertical + stores"]
+          "blur h + v (MFMA) + stores (+ atomic)", "Harris", "fallback: blur vertical + stores"]
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
+    ap.add_argument("--lib", default=os.path.join(ROOT, "ya_vo_amd", "lib", "libyavo_prof.so"),
+                    help="a profiling build (YAVO_LM_PROFILE), e.g. one of another revision's kernels for an A/B")
     args = ap.parse_args()
-    lib = yv.load_library(os.path.join(ROOT, "ya_vo_amd", "lib", "libyavo_prof.so"))
+    lib = yv.load_library(args.lib)
     lib.yv_debug_det_prof.argtypes = [ctypes.c_void_p]
     H, W, B = 376, 1241, args.frames
     ctx = yv.Context(0)

@@ -215,8 +215,8 @@ struct K9 {
     // sum of the taps <= 256: every rounded output (acc + 2^15) >> 16 is <= 255 and acc < 2^24, so the output byte
     // is byte 2 of the accumulator and needs no clamp (OpenCV's bit-exact kernels sum to exactly 256)
     int byte2;
-    // horizontal pass on the int8 matrix cores (every tap <= 127): pixels enter as p - 128, so the sums are offset by
-    // 128 * (sum of the taps), the accumulators' start value
+    // both passes on the int8 matrix cores (every tap <= 127, the taps sum to 256): pixels and the bytes of h enter as
+    // b - 128, so the sums are offset by hbias = 128 * (sum of the taps)
     int mfma;
     int hbias;
 };
@@ -239,7 +239,7 @@ static K9 make_k9(const uint16_t* k9) {
     kw.byte2 = sum <= 256 ? 1 : 0;
     uint32_t mx = 0;
     for (int i = 0; i < 9; ++i) mx = k9[i] > mx ? k9[i] : mx;
-    kw.mfma = mx <= 127 ? 1 : 0;
+    kw.mfma = (mx <= 127 && sum == 256) ? 1 : 0;
     kw.hbias = (int)(128 * sum);
     return kw;
 }
@@ -303,14 +303,17 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
                                                      int64_t cap, uint32_t* __restrict__ cand_count, K9 kw,
                                                      uint8_t* __restrict__ blur) {
     __shared__ __align__(16) uint8_t tile[FT_LH * FT_LW];
-    // the pretest survivors (phases 1-2) and the horizontal blur (from the barrier after phase 2) share LDS
+    // the pretest survivors (phases 1-2) share LDS with what the blur keeps there from the barrier after phase 2 on:
+    // the output bytes on their way to 64-B row stores (matrix-core path) or the horizontal sums (fallback path)
     constexpr int kPreDw = FT_W * FT_H / 2, kHbufDw = kBlur ? (FT_LH / 2) * FT_W : 0;
     __shared__ __align__(16) uint32_t s_share[kPreDw > kHbufDw ? kPreDw : kHbufDw];
     uint16_t* s_pre = reinterpret_cast<uint16_t*>(s_share);
     uint32_t* hbuf = s_share;
     __shared__ uint16_t s_pos[FT_W * FT_H];
     __shared__ uint32_t s_n, s_npre, s_base;
-    __shared__ uint32_t s_band[4 * 9];  // kh[r][M] at r * 9 + M + 3 for M in -3 .. 5 (0 outside 0 .. 2): the B operand
+    // kh[r][M] at r * kBandM + M + 3 for M in -3 .. 15 (0 outside 0 .. 2): the banded tap operands, read with no test
+    constexpr int kBandM = 19;
+    __shared__ uint32_t s_band[4 * kBandM];
     DP_DECL
     // 1-D grid, XCD-aware: an image's tiles (and the halo rows neighbouring tiles share) stay in one XCD's L2
     const int ntx = (W + FT_W - 1) / FT_W, nty = (H + FT_H - 1) / FT_H;
@@ -325,8 +328,8 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
         s_n = 0;
         s_npre = 0;
     }
-    if (kBlur && tid < 4 * 9) {
-        const int r = tid / 9, M = tid - 9 * r - 3;
+    if (kBlur && tid < 4 * kBandM) {
+        const int r = tid / kBandM, M = tid - kBandM * r - 3;
         uint32_t v = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
@@ -491,45 +494,125 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
     __syncthreads();
     DP_MARK(2);
     const uint32_t n = s_n;
-    // one global atomic per workgroup reserves the output range of this tile's corners
-    if (tid == 0 && n > 0) s_base = atomicAdd(&cand_count[img], n);
-    if (kBlur && kw.mfma) {
-        // horizontal pass on the int8 matrix cores: the 64 x 64 h of the tile (all 64 LDS rows, the 64 output
-        // columns) is 4 x 4 blocks of 16 x 16, block (rb, cb) = A (tile rows 16 rb .., LDS columns 16 cb .. 16 cb + 63,
-        // as p - 128) x B (the banded taps: B[k][n] = tap(k - n)), one v_mfma_i32_16x16x64_i8 each, wave rb taking
-        // row block rb.  Exact: |products| and sums are integers far inside i32, and the accumulators start at
-        // 128 * sum(taps), so acc = sum_t tap(t) p[x + t] (<= 65280: 16 bits).  A lane (n, g) of K-block g holds
-        // bytes 16 g .. 16 g + 15 of its row / column for A and B alike (the pairing is by K index, the same for
-        // both); B's dword jj is kh[n & 3][4 g + jj - (n >> 2)] (0 outside 0 .. 2), read from s_band.  LDS columns
-        // past 71 (cb = 3) meet zero taps.  Output lane (n, g) holds rows 4 g .. 4 g + 3 of column n: rows 4g, 4g + 1
-        // pack into h row pair 8 rb + 2 g, as the vertical pass reads them.  VALU per wave: 4 x (4 xor + 2 packs)
-        // where the v_dot4 form took ~60: detect alone 2.766 -> 2.743 ms (profiles/r06/c41).  The four lane groups'
-        // row pairs share banks (4-way conflicts on these 8 stores); a 72-dword row-pair stride cost 1 KB of LDS and
-        // the 8th workgroup per CU (2.92 ms), an XOR swizzle of the column groups cost the vertical pass more VALU than
-        // the conflicts (2.82 ms; c42-c44).
-        typedef int dt_v4i __attribute__((ext_vector_type(4)));
-        const int n = lane & 15, g = lane >> 4;
-        dt_v4i B;
+    // Harris response of every staged corner, one lane per corner (no divergence across FAST lanes);
+    // consecutive lanes write consecutive keys from `base`, the tile's range in the image's candidate list
+    auto harris = [&](uint32_t base) {
+        uint64_t* out = cand_keys + (int64_t)img * cap + base;
+        for (uint32_t i = tid; i < n; i += 256) {
+            const int pos = s_pos[i];
+            const int prr = pos >> 6, ptx = pos & 63;
+            // the 5 x 5 patch's top-left: every read is this base plus a constant non-negative offset
+            const uint8_t* t0 = &tile[(prr + FT_R - 2) * FT_LW + ptx + FT_R - 2];
+            // Sobel Ix / Iy (3x3 correlation) at the 3x3 window around the corner, from the 5x5 patch.
+            int sxx = 0, sxy = 0, syy = 0;
 #pragma unroll
-        for (int jj = 0; jj < 4; ++jj) {
-            const int M = 4 * g + jj - (n >> 2);
-            B[jj] = (M >= -3 && M <= 5) ? (int)s_band[(n & 3) * 9 + M + 3] : 0;
+            for (int ii = -1; ii <= 1; ++ii) {
+#pragma unroll
+                for (int j = -1; j <= 1; ++j) {
+                    const uint8_t* q = t0 + (ii + 2) * FT_LW + j + 2;
+                    const int pmm = q[-FT_LW - 1], pm0 = q[-FT_LW], pmp = q[-FT_LW + 1];
+                    const int p0m = q[-1], p0p = q[1];
+                    const int ppm = q[FT_LW - 1], pp0 = q[FT_LW], ppp = q[FT_LW + 1];
+                    const int gx = (pmp - pmm) + 2 * (p0p - p0m) + (ppp - ppm);
+                    const int gy = (ppm - pmm) + 2 * (pp0 - pm0) + (ppp - pmp);
+                    sxx += gx * gx;
+                    sxy += gx * gy;
+                    syy += gy * gy;
+                }
+            }
+            // all partial sums are integers < 2^24: exact in float, as in the reference
+            const float resp = harris_response((float)sxx, (float)sxy, (float)syy, eig);
+            out[i] = make_key(resp, (uint32_t)((r0 + prr) * W + (c0 + ptx)));  // cap >= every pixel: in range
         }
-        const dt_v4i C = {kw.hbias, kw.hbias, kw.hbias, kw.hbias};
-        const int rb = ty;
-        const uint8_t* arow = &tile[(16 * rb + n) * FT_LW + 16 * g];
+    };
+    if (kBlur && kw.mfma) {
+        // Both blur passes on the int8 matrix cores, h never leaving registers (every tap <= 127 and the taps sum to
+        // 256, yv_set_blur_kernel's contract).  One global atomic per workgroup reserves the output range of this
+        // tile's corners; it is issued first and its latency hides behind the blur.
+        if (tid == 0 && n > 0) s_base = atomicAdd(&cand_count[img], n);
+        // Horizontal: the 64 x 64 h of the tile (all 64 LDS rows, the 64 output columns) is 4 x 4 blocks of 16 x 16,
+        // block (rb, cb) = A (tile rows 16 rb .., LDS columns 16 cb .. 16 cb + 63, as p - 128) x B (the banded taps:
+        // B[k][n] = tap(k - n)), one v_mfma_i32_16x16x64_i8 each, wave cb taking COLUMN block cb.  Exact: products and
+        // sums are integers far inside i32.  A lane (n, g) of K-block g holds bytes 16 g .. 16 g + 15 of its row /
+        // column for A and B alike (the pairing is by K index, the same for both); B's dword jj is kh[n & 3][4 g + jj -
+        // (n >> 2)] (0 outside 0 .. 2), read from s_band.  LDS columns past 71 (cb = 3) meet zero taps.  The
+        // accumulators start at 0, so acc = h - 128 * 256 with h = sum_t tap(t) p[x + t] <= 65280: a signed 16-bit
+        // value whose low byte is h's and whose high byte is h's high byte - 128, already the int8 the next MFMA wants.
+        // Output lane (n, g) holds acc[rb][i] = h(LDS row 16 rb + 4 g + i, column 16 cb + n): 16 rows of one column,
+        // the four lane groups of a column all 64.
+        typedef int dt_v4i __attribute__((ext_vector_type(4)));
+        const int nn = lane & 15, g = lane >> 4;
+        const uint32_t* band = &s_band[(nn & 3) * kBandM + 3 - (nn >> 2)];  // band[M + (n >> 2)] = kh[n & 3][M]
+        const dt_v4i B = {(int)band[4 * g], (int)band[4 * g + 1], (int)band[4 * g + 2], (int)band[4 * g + 3]};
+        const dt_v4i Z = {0, 0, 0, 0};
+        const int cb = ty;
+        const uint8_t* arow = &tile[nn * FT_LW + 16 * cb + 16 * g];
+        // Vertical: out(r, x) = sum_t tap(t) h(r + t, x) over the same K = 64 LDS rows, so those accumulators ARE an
+        // MFMA operand once split into bytes, h = 256 hi + lo (each byte as b - 128, like the pixels): K slot (g, j)
+        // of lane (n, g) is LDS row 16 (j >> 2) + 4 g + (j & 3) -- dword rb holds the four bytes of acc[rb][0 .. 3].
+        // K need not be in row order, the tap operand only has to use the same labelling.
+        dt_v4i Hlo, Hhi;
 #pragma unroll
-        for (int cb = 0; cb < 4; ++cb) {
-            const uint2 lo = *reinterpret_cast<const uint2*>(arow + 16 * cb);
-            const uint2 hi = *reinterpret_cast<const uint2*>(arow + 16 * cb + 8);
+        for (int rb = 0; rb < 4; ++rb) {
+            const uint2 lo = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW);
+            const uint2 hi = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW + 8);
             const dt_v4i A = {(int)(lo.x ^ 0x80808080u), (int)(lo.y ^ 0x80808080u), (int)(hi.x ^ 0x80808080u),
                               (int)(hi.y ^ 0x80808080u)};
-            const dt_v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, C, 0, 0, 0);
-            const int q = 8 * rb + 2 * g, x = 16 * cb + n;
-            hbuf[q * FT_W + x] = (uint32_t)acc[0] | ((uint32_t)acc[1] << 16);
-            hbuf[(q + 1) * FT_W + x] = (uint32_t)acc[2] | ((uint32_t)acc[3] << 16);
+            const dt_v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, Z, 0, 0, 0);
+            // bytes 0 and 1 of the four accumulators, transposed: {lo0, lo1, hi0, hi1}, {lo2, lo3, hi2, hi3}
+            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x05010400u);
+            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x05010400u);
+            Hlo[rb] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
+            Hhi[rb] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
         }
-    } else if (kBlur) {
+        // The product is taken transposed, D[column][row] = H^T x T^T with H as A: lane (x, g) ends with output row
+        // 16 ob + x, columns 16 cb + 4 g .. + 3 as one dword.  The tap operand of output-row block ob: byte j of lane
+        // (x, g) is tap(row(g, j) - (16 ob + x)), so dword jj is the four taps from 16 (jj - ob) + 4 g - x
+        // = kh[x & 3][4 (jj - ob) + g - (x >> 2)], non-zero only for jj - ob in {0, 1}: two registers from s_band serve
+        // every ob.  Output row r reads LDS rows r .. r + 8 (all inside the 64 for the 56 stored rows), so every stored
+        // row sees all nine taps: sum = 256 (vh + 128 * 256) + (vl + 128 * 256), and the start value of vl carries
+        // both terms and 2^15, the rounding term of (sum + 2^15) >> 16.  The output byte is byte 2 (sum < 2^24).
+        const int T0 = (int)band[g], T1 = (int)band[g + 4];
+        const int cv = 257 * kw.hbias + (1 << 15);
+        const dt_v4i Cv = {cv, cv, cv, cv};
+        // The bytes go through the LDS the pretest list no longer needs, so that the global stores are whole 64-B row
+        // segments: row R's 16 dwords at s_share[16 R ..], the 16-B column groups XORed with (R >> 2) & 3 so that the
+        // 64 lanes of a store instruction (16 rows x 4 dwords) hit 64 different banks.
+        uint32_t* ostage = &s_share[nn * 16 + ((4 * cb) ^ (nn & 12)) + g];
+#pragma unroll
+        for (int ob = 0; ob < 4; ++ob) {
+            dt_v4i T = {0, 0, 0, 0};
+            T[ob] = T0;
+            if (ob < 3) T[ob + 1] = T1;
+            const dt_v4i vl = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hlo, T, Cv, 0, 0, 0);
+            const dt_v4i vh = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hhi, T, Z, 0, 0, 0);
+            uint32_t v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = ((uint32_t)vh[i] << 8) + (uint32_t)vl[i];
+            // two v_perm pick the byte 2s pairwise, one v_perm joins the pairs
+            ostage[ob * 16 * 16] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u),
+                                                         __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u), 0x05040100u);
+        }
+        __syncthreads();  // publishes s_base too
+        // 4 lanes per row, 16 B each; rows past the tile (the upper half of ob = 3) and past the image are not stored,
+        // columns past W land in the row padding
+        if (tid < FT_H * 4) {
+            const int R = tid >> 2, q = tid & 3;
+            const int bp = blur_pitch(W);
+            if (r0 + R < H)
+                *reinterpret_cast<uint4*>(blur + ((int64_t)img * H + r0 + R) * bp + c0 + 16 * (q ^ ((R >> 2) & 3))) =
+                    *reinterpret_cast<const uint4*>(&s_share[R * 16 + 4 * q]);
+        }
+        DP_MARK(3);
+        if (n > 0) harris(s_base);
+        DP_MARK(4);
+        DP_STORE();
+        return;
+    }
+    // No blur, or a tap above 127 (does not fit int8): the v_dot4 horizontal and v_dot2 vertical passes, h through LDS.
+    // One global atomic per workgroup reserves the output range of this tile's corners.
+    if (tid == 0 && n > 0) s_base = atomicAdd(&cand_count[img], n);
+    if (kBlur) {
         // horizontal pass, exact: h = sum_j k_j * p[x + j] as two v_dot4_u32_u8 + one mad on the byte row
         // (rows start 4-byte aligned: FT_LW = 72).  h <= 255 * 256 fits 16 bits; rows 2q and 2q+1 are
         // packed into one dword so the vertical pass can use v_dot2_u32_u16.  One item = 4 adjacent
@@ -557,37 +640,7 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
     }
     __syncthreads();
     DP_MARK(3);
-    // Harris response of every staged corner, one lane per corner (no divergence across FAST lanes);
-    // consecutive lanes write consecutive keys
-    if (n > 0) {
-        uint64_t* out = cand_keys + (int64_t)img * cap + s_base;
-        for (uint32_t i = tid; i < n; i += 256) {
-            const int pos = s_pos[i];
-            const int prr = pos >> 6, ptx = pos & 63;
-            // the 5 x 5 patch's top-left: every read is this base plus a constant non-negative offset
-            const uint8_t* t0 = &tile[(prr + FT_R - 2) * FT_LW + ptx + FT_R - 2];
-            // Sobel Ix / Iy (3x3 correlation) at the 3x3 window around the corner, from the 5x5 patch.
-            int sxx = 0, sxy = 0, syy = 0;
-#pragma unroll
-            for (int ii = -1; ii <= 1; ++ii) {
-#pragma unroll
-                for (int j = -1; j <= 1; ++j) {
-                    const uint8_t* q = t0 + (ii + 2) * FT_LW + j + 2;
-                    const int pmm = q[-FT_LW - 1], pm0 = q[-FT_LW], pmp = q[-FT_LW + 1];
-                    const int p0m = q[-1], p0p = q[1];
-                    const int ppm = q[FT_LW - 1], pp0 = q[FT_LW], ppp = q[FT_LW + 1];
-                    const int gx = (pmp - pmm) + 2 * (p0p - p0m) + (ppp - ppm);
-                    const int gy = (ppm - pmm) + 2 * (pp0 - pm0) + (ppp - pmp);
-                    sxx += gx * gx;
-                    sxy += gx * gy;
-                    syy += gy * gy;
-                }
-            }
-            // all partial sums are integers < 2^24: exact in float, as in the reference
-            const float resp = harris_response((float)sxx, (float)sxy, (float)syy, eig);
-            out[i] = make_key(resp, (uint32_t)((r0 + prr) * W + (c0 + ptx)));  // cap >= every pixel: in range
-        }
-    }
+    if (n > 0) harris(s_base);
     DP_MARK(4);
     if (kBlur) {
         // vertical pass, exact u32: rows 2m and 2m+1 of columns xq..xq+3 from the row-pair dwords P_m .. P_{m+4}
