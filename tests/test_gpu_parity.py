@@ -228,9 +228,10 @@ def _device_frames(ctx, frames):
 
 @pytest.mark.parametrize("k9", [[2, 9, 25, 44, 96, 44, 25, 9, 2], [0, 0, 0, 28, 200, 28, 0, 0, 0]])
 def test_batch_blur_custom_taps(ctx, oracle, k9):
-    """The detect kernel's fused blur with other tap sets (yv_set_blur_kernel): taps <= 127 take the int8
-    matrix-core horizontal pass (its accumulator bias is 128 x the taps' sum), a tap above 127 the v_dot4 form; both
-    byte-equal to the oracle's blur with the same taps, a border image shape included."""
+    """The batch's blur with other tap sets (yv_set_blur_kernel): taps <= 127 take the detect kernel's fused int8
+    matrix-core blur (its accumulator bias is 128 x the taps' sum), a tap above 127 the detect kernel without blur
+    followed by the stand-alone blur kernel; both byte-equal to the oracle's blur with the same taps, a border image
+    shape included."""
     import torch  # noqa: F401
     default = np.array(yv.DEFAULT_BLUR_KERNEL, np.uint16)
     for H, W in ((376, 1241), (77, 150)):

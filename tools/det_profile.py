@@ -15,10 +15,10 @@ import torch  # noqa: E402
 import ya_vo_amd as yv  # noqa: E402
 from ya_vo_amd.synth import synth_stereo_batch  # noqa: E402
 
-# taps <= 127 (the default): both blur passes run on the matrix cores in one phase and the kernel ends after Harris;
-# the last phase is the v_dot2 vertical pass of the fallback path (a tap above 127), whose phase 3 is its horizontal pass
+# the five phases of detect_kernel<true> (taps <= 127, the default).  g_det_prof has six slots per workgroup: the last
+# is 0 at this code and the second blur phase in a profiling build of a revision that still had the v_dot2 pass
 PHASES = ["stage tile (loads + LDS)", "FAST phase 1 (pretest)", "FAST phase 2 (full test)",
-          "blur h + v (MFMA) + stores (+ atomic)", "Harris", "fallback: blur vertical + stores"]
+          "blur h + v (MFMA) + stores (+ atomic)", "Harris"]
 
 
 def main():

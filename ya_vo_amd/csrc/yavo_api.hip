@@ -552,7 +552,7 @@ int yv_set_blur_kernel(yv_ctx* ctx, const uint16_t* k9) {
     if (!ctx || !k9) return YV_ERR_INVALID;
     uint32_t sum = 0;
     for (int i = 0; i < 9; ++i) {
-        if (k9[i] > 255u) return YV_ERR_INVALID;  // taps are packed as u8 for v_dot4_u32_u8
+        if (k9[i] > 255u) return YV_ERR_INVALID;  // the ABI's documented bound (yavo.h)
         sum += k9[i];
     }
     if (sum != 256u) return YV_ERR_INVALID;  // 8 fractional bits: the kernel must sum to 1.0

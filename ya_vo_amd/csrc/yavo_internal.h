@@ -54,7 +54,9 @@ struct Desc {                      // 256-bit BRIEF descriptor, test j -> bit j 
 void launch_fast_harris(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch,
                         int thr, int eig, uint64_t* cand_keys, int64_t cap, uint32_t* cand_count,
                         hipStream_t s);
-// Fused FAST + Harris + 9x9 blur over the same LDS tile (the image is read once).
+// FAST + Harris + 9x9 blur (k9_host: 9 taps that sum to 256).  Taps <= 127: one fused kernel over the same LDS tile,
+// the blur on the int8 matrix cores (the image is read once).  A tap above 127: launch_fast_harris, then launch_blur9
+// on the same stream.
 void launch_detect_blur(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch, int thr,
                         int eig, uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, const uint16_t* k9_host,
                         uint8_t* blur, hipStream_t s);

@@ -203,21 +203,12 @@ __device__ __forceinline__ float key_resp(uint64_t key) {
 }
 
 struct K9 {
-    uint32_t k[9];
-    // horizontal pass: output column j (0..3) of a 4-column item is dot4(d0, kh[j][0]) + dot4(d1, kh[j][1]) +
-    // dot4(d2, kh[j][2]) over the row's 3 aligned LDS dwords d0..d2 (bytes 0..11): byte i of kh[j][m] is tap
-    // 4m + i - j (0 outside 0..8), so no byte of the row is shifted or extracted in VALU
+    uint32_t k[9];  // the taps (blur9_kernel)
+    // detect_kernel<true>'s band table: byte i of kh[j][m] is tap 4m + i - j (0 outside 0..8), the four taps a dword of
+    // either matrix-core tap operand holds
     uint32_t kh[4][3];
-    // vertical pass over row-pair dwords P_t = {h[2m + 2t] (lo16), h[2m + 2t + 1] (hi16)}, t = 0..4:
-    // even output row 2m = sum_t dot2(P_t, kve[t]), odd row 2m + 1 = sum_t dot2(P_t, kvo[t])
-    uint32_t kve[5];  // (k0,k1) (k2,k3) (k4,k5) (k6,k7) (k8,0)
-    uint32_t kvo[5];  // (0,k0) (k1,k2) (k3,k4) (k5,k6) (k7,k8)
-    // sum of the taps <= 256: every rounded output (acc + 2^15) >> 16 is <= 255 and acc < 2^24, so the output byte
-    // is byte 2 of the accumulator and needs no clamp (OpenCV's bit-exact kernels sum to exactly 256)
-    int byte2;
-    // both passes on the int8 matrix cores (every tap <= 127, the taps sum to 256): pixels and the bytes of h enter as
-    // b - 128, so the sums are offset by hbias = 128 * (sum of the taps)
-    int mfma;
+    // the matrix-core passes take pixels and the bytes of h as b - 128, so the sums are offset by hbias = 128 * (sum of
+    // the taps)
     int hbias;
 };
 
@@ -232,14 +223,6 @@ static K9 make_k9(const uint16_t* k9) {
     for (int j = 0; j < 4; ++j)
         for (int m = 0; m < 3; ++m)
             for (int i = 0; i < 4; ++i) kw.kh[j][m] |= tap(4 * m + i - j) << (8 * i);
-    for (int t = 0; t < 5; ++t) {
-        kw.kve[t] = tap(2 * t) | (tap(2 * t + 1) << 16);
-        kw.kvo[t] = tap(2 * t - 1) | (tap(2 * t) << 16);
-    }
-    kw.byte2 = sum <= 256 ? 1 : 0;
-    uint32_t mx = 0;
-    for (int i = 0; i < 9; ++i) mx = k9[i] > mx ? k9[i] : mx;
-    kw.mfma = (mx <= 127 && sum == 256) ? 1 : 0;
     kw.hbias = (int)(128 * sum);
     return kw;
 }
@@ -251,12 +234,13 @@ __device__ __forceinline__ int reflect101(int p, int len) {
     return p;
 }
 
-// Fused per-tile detector: FAST-12 candidate test + Harris response (src/FastDetector.cc:298-335) and the
-// 9x9 fixed-point Gaussian of the same tile (src/BriefDescriptor.cc:90), so the image is read from HBM
-// once.  One 256-thread workgroup per 64 x 32 output tile, the tile plus a 4-pixel halo staged in LDS
-// (BORDER_REFLECT_101 values outside the image: the blur needs them, no FAST candidate ever reads them).
+// Fused per-tile detector: FAST-12 candidate test + Harris response (src/FastDetector.cc:298-335) and, with kBlur
+// (the fused matrix-core blur), the 9x9 fixed-point Gaussian of the same tile (src/BriefDescriptor.cc:90), so the
+// image is read from HBM once.  One 256-thread workgroup per 64 x 56 output tile, the tile plus a 4-pixel halo staged
+// in LDS (BORDER_REFLECT_101 values outside the image: the blur needs them, no FAST candidate ever reads them).
 // Candidates are staged in LDS and appended with ONE global atomic per workgroup.
-// YAVO_LM_PROFILE builds (tools/det_profile.py): detect phase cycles of lane 0 of every workgroup, summed
+// YAVO_LM_PROFILE builds (tools/det_profile.py): detect phase cycles of lane 0 of every workgroup, summed (five
+// phases; g_det_prof keeps six slots, the last 0, so that the tool also reads a build of an earlier revision)
 #ifdef YAVO_LM_PROFILE
 constexpr int kDetProfSlots = 131072;
 __device__ unsigned long long g_det_prof[kDetProfSlots][6];
@@ -266,12 +250,6 @@ __device__ unsigned long long g_det_prof[kDetProfSlots][6];
         const unsigned slot_ = blockIdx.x; \
         if (threadIdx.x == 0 && slot_ < kDetProfSlots) for (int q_ = 0; q_ < 6; ++q_) g_det_prof[slot_][q_] = dp_acc[q_]; \
     } while (0)
-#else
-#define DP_DECL
-#define DP_MARK(k) do {} while (0)
-#define DP_STORE() do {} while (0)
-#endif
-#ifdef YAVO_LM_PROFILE
 constexpr int kBriefProfSlots = 16384;
 __device__ unsigned long long g_brief_prof[kBriefProfSlots][6];
 #define BP_DECL unsigned long long bp_acc[4] = {0, 0, 0, 0}; unsigned long long bp_t = __builtin_readcyclecounter(); \
@@ -287,6 +265,9 @@ __device__ unsigned long long g_brief_prof[kBriefProfSlots][6];
         } \
     } while (0)
 #else
+#define DP_DECL
+#define DP_MARK(k) do {} while (0)
+#define DP_STORE() do {} while (0)
 #define BP_DECL
 #define BP_MARK(k) do {} while (0)
 #define BP_STORE() do {} while (0)
@@ -296,6 +277,90 @@ constexpr int FT_H = kFastTileH;        // 56 output rows per tile
 constexpr int FT_R = 4;                 // halo: blur radius 4 (ring radius 3, Sobel + 3x3 window radius 2)
 constexpr int FT_LW = FT_W + 2 * FT_R;  // 72 bytes per LDS row
 constexpr int FT_LH = FT_H + 2 * FT_R;  // 64 LDS rows
+constexpr int kBandM = 19;              // dwords per row of the band table (detect_kernel's s_band)
+constexpr int kBlurStageDw = FT_LH * (FT_W / 4);  // the blur's output staging: 4 row blocks of 16 rows, 16 dwords each
+
+// detect_kernel<true>'s 9x9 blur of the staged tile, both passes on the int8 matrix cores with h never leaving
+// registers (every tap <= 127 and the taps sum to 256: launch_detect_blur's dispatch).  Wave cb takes column block cb
+// and leaves the tile's output bytes in `stage`; after a barrier blur_store_rows writes them out.
+__device__ __forceinline__ void blur_tile_mfma(const uint8_t* tile, const uint32_t* s_band, uint32_t* stage, int hbias,
+                                               int lane, int cb) {
+    // Horizontal: the 64 x 64 h of the tile (all 64 LDS rows, the 64 output columns) is 4 x 4 blocks of 16 x 16,
+    // block (rb, cb) = A (tile rows 16 rb .., LDS columns 16 cb .. 16 cb + 63, as p - 128) x B (the banded taps:
+    // B[k][n] = tap(k - n)), one v_mfma_i32_16x16x64_i8 each, wave cb taking COLUMN block cb.  Exact: products and
+    // sums are integers far inside i32.  A lane (n, g) of K-block g holds bytes 16 g .. 16 g + 15 of its row /
+    // column for A and B alike (the pairing is by K index, the same for both); B's dword jj is kh[n & 3][4 g + jj -
+    // (n >> 2)] (0 outside 0 .. 2), read from s_band.  LDS columns past 71 (cb = 3) meet zero taps.  The
+    // accumulators start at 0, so acc = h - 128 * 256 with h = sum_t tap(t) p[x + t] <= 65280: a signed 16-bit
+    // value whose low byte is h's and whose high byte is h's high byte - 128, already the int8 the next MFMA wants.
+    // Output lane (n, g) holds acc[rb][i] = h(LDS row 16 rb + 4 g + i, column 16 cb + n): 16 rows of one column,
+    // the four lane groups of a column all 64.
+    typedef int dt_v4i __attribute__((ext_vector_type(4)));
+    const int nn = lane & 15, g = lane >> 4;
+    const uint32_t* band = &s_band[(nn & 3) * kBandM + 3 - (nn >> 2)];  // band[M + (n >> 2)] = kh[n & 3][M]
+    const dt_v4i B = {(int)band[4 * g], (int)band[4 * g + 1], (int)band[4 * g + 2], (int)band[4 * g + 3]};
+    const dt_v4i Z = {0, 0, 0, 0};
+    const uint8_t* arow = &tile[nn * FT_LW + 16 * cb + 16 * g];
+    // Vertical: out(r, x) = sum_t tap(t) h(r + t, x) over the same K = 64 LDS rows, so those accumulators ARE an
+    // MFMA operand once split into bytes, h = 256 hi + lo (each byte as b - 128, like the pixels): K slot (g, j)
+    // of lane (n, g) is LDS row 16 (j >> 2) + 4 g + (j & 3) -- dword rb holds the four bytes of acc[rb][0 .. 3].
+    // K need not be in row order, the tap operand only has to use the same labelling.
+    dt_v4i Hlo, Hhi;
+#pragma unroll
+    for (int rb = 0; rb < 4; ++rb) {
+        const uint2 lo = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW);
+        const uint2 hi = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW + 8);
+        const dt_v4i A = {(int)(lo.x ^ 0x80808080u), (int)(lo.y ^ 0x80808080u), (int)(hi.x ^ 0x80808080u),
+                          (int)(hi.y ^ 0x80808080u)};
+        const dt_v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, Z, 0, 0, 0);
+        // bytes 0 and 1 of the four accumulators, transposed: {lo0, lo1, hi0, hi1}, {lo2, lo3, hi2, hi3}
+        const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x05010400u);
+        const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x05010400u);
+        Hlo[rb] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
+        Hhi[rb] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
+    }
+    // The product is taken transposed, D[column][row] = H^T x T^T with H as A: lane (x, g) ends with output row
+    // 16 ob + x, columns 16 cb + 4 g .. + 3 as one dword.  The tap operand of output-row block ob: byte j of lane
+    // (x, g) is tap(row(g, j) - (16 ob + x)), so dword jj is the four taps from 16 (jj - ob) + 4 g - x
+    // = kh[x & 3][4 (jj - ob) + g - (x >> 2)], non-zero only for jj - ob in {0, 1}: two registers from s_band serve
+    // every ob.  Output row r reads LDS rows r .. r + 8 (all inside the 64 for the 56 stored rows), so every stored
+    // row sees all nine taps: sum = 256 (vh + 128 * 256) + (vl + 128 * 256), and the start value of vl carries
+    // both terms and 2^15, the rounding term of (sum + 2^15) >> 16.  The output byte is byte 2 (sum < 2^24).
+    const int T0 = (int)band[g], T1 = (int)band[g + 4];
+    const int cv = 257 * hbias + (1 << 15);
+    const dt_v4i Cv = {cv, cv, cv, cv};
+    // The bytes go through the LDS the pretest list no longer needs, so that the global stores are whole 64-B row
+    // segments: row R's 16 dwords at stage[16 R ..], the 16-B column groups XORed with (R >> 2) & 3 so that the
+    // 64 lanes of a store instruction (16 rows x 4 dwords) hit 64 different banks.
+    uint32_t* ostage = &stage[nn * 16 + ((4 * cb) ^ (nn & 12)) + g];
+#pragma unroll
+    for (int ob = 0; ob < 4; ++ob) {
+        dt_v4i T = {0, 0, 0, 0};
+        T[ob] = T0;
+        if (ob < 3) T[ob + 1] = T1;
+        const dt_v4i vl = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hlo, T, Cv, 0, 0, 0);
+        const dt_v4i vh = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hhi, T, Z, 0, 0, 0);
+        uint32_t v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = ((uint32_t)vh[i] << 8) + (uint32_t)vl[i];
+        // two v_perm pick the byte 2s pairwise, one v_perm joins the pairs
+        ostage[ob * 16 * 16] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u),
+                                                     __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u), 0x05040100u);
+    }
+}
+
+// The staged rows to the pitched blurred image: 4 lanes per row, 16 B each; rows past the tile (the upper half of
+// ob = 3) and past the image are not stored, columns past W land in the row padding.
+__device__ __forceinline__ void blur_store_rows(const uint32_t* stage, uint8_t* __restrict__ blur, int img, int H, int W,
+                                                int r0, int c0, int tid) {
+    if (tid < FT_H * 4) {
+        const int R = tid >> 2, q = tid & 3;
+        const int bp = blur_pitch(W);
+        if (r0 + R < H)
+            *reinterpret_cast<uint4*>(blur + ((int64_t)img * H + r0 + R) * bp + c0 + 16 * (q ^ ((R >> 2) & 3))) =
+                *reinterpret_cast<const uint4*>(&stage[R * 16 + 4 * q]);
+    }
+}
 
 template <bool kBlur>
 __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__ imgs, int H, int W, int stride,
@@ -303,16 +368,15 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
                                                      int64_t cap, uint32_t* __restrict__ cand_count, K9 kw,
                                                      uint8_t* __restrict__ blur) {
     __shared__ __align__(16) uint8_t tile[FT_LH * FT_LW];
-    // the pretest survivors (phases 1-2) share LDS with what the blur keeps there from the barrier after phase 2 on:
-    // the output bytes on their way to 64-B row stores (matrix-core path) or the horizontal sums (fallback path)
-    constexpr int kPreDw = FT_W * FT_H / 2, kHbufDw = kBlur ? (FT_LH / 2) * FT_W : 0;
-    __shared__ __align__(16) uint32_t s_share[kPreDw > kHbufDw ? kPreDw : kHbufDw];
+    // the pretest survivors (phases 1-2) share LDS with the blur's output bytes on their way to 64-B row stores, which
+    // are written from the barrier after phase 2 on
+    constexpr int kPreDw = FT_W * FT_H / 2;
+    static_assert(kBlurStageDw <= kPreDw, "the blur's output staging must fit in the pretest list");
+    __shared__ __align__(16) uint32_t s_share[kPreDw];
     uint16_t* s_pre = reinterpret_cast<uint16_t*>(s_share);
-    uint32_t* hbuf = s_share;
     __shared__ uint16_t s_pos[FT_W * FT_H];
     __shared__ uint32_t s_n, s_npre, s_base;
     // kh[r][M] at r * kBandM + M + 3 for M in -3 .. 15 (0 outside 0 .. 2): the banded tap operands, read with no test
-    constexpr int kBandM = 19;
     __shared__ uint32_t s_band[4 * kBandM];
     DP_DECL
     // 1-D grid, XCD-aware: an image's tiles (and the halo rows neighbouring tiles share) stay in one XCD's L2
@@ -525,178 +589,15 @@ __global__ __launch_bounds__(256) void detect_kernel(const uint8_t* __restrict__
             out[i] = make_key(resp, (uint32_t)((r0 + prr) * W + (c0 + ptx)));  // cap >= every pixel: in range
         }
     };
-    if (kBlur && kw.mfma) {
-        // Both blur passes on the int8 matrix cores, h never leaving registers (every tap <= 127 and the taps sum to
-        // 256, yv_set_blur_kernel's contract).  One global atomic per workgroup reserves the output range of this
-        // tile's corners; it is issued first and its latency hides behind the blur.
-        if (tid == 0 && n > 0) s_base = atomicAdd(&cand_count[img], n);
-        // Horizontal: the 64 x 64 h of the tile (all 64 LDS rows, the 64 output columns) is 4 x 4 blocks of 16 x 16,
-        // block (rb, cb) = A (tile rows 16 rb .., LDS columns 16 cb .. 16 cb + 63, as p - 128) x B (the banded taps:
-        // B[k][n] = tap(k - n)), one v_mfma_i32_16x16x64_i8 each, wave cb taking COLUMN block cb.  Exact: products and
-        // sums are integers far inside i32.  A lane (n, g) of K-block g holds bytes 16 g .. 16 g + 15 of its row /
-        // column for A and B alike (the pairing is by K index, the same for both); B's dword jj is kh[n & 3][4 g + jj -
-        // (n >> 2)] (0 outside 0 .. 2), read from s_band.  LDS columns past 71 (cb = 3) meet zero taps.  The
-        // accumulators start at 0, so acc = h - 128 * 256 with h = sum_t tap(t) p[x + t] <= 65280: a signed 16-bit
-        // value whose low byte is h's and whose high byte is h's high byte - 128, already the int8 the next MFMA wants.
-        // Output lane (n, g) holds acc[rb][i] = h(LDS row 16 rb + 4 g + i, column 16 cb + n): 16 rows of one column,
-        // the four lane groups of a column all 64.
-        typedef int dt_v4i __attribute__((ext_vector_type(4)));
-        const int nn = lane & 15, g = lane >> 4;
-        const uint32_t* band = &s_band[(nn & 3) * kBandM + 3 - (nn >> 2)];  // band[M + (n >> 2)] = kh[n & 3][M]
-        const dt_v4i B = {(int)band[4 * g], (int)band[4 * g + 1], (int)band[4 * g + 2], (int)band[4 * g + 3]};
-        const dt_v4i Z = {0, 0, 0, 0};
-        const int cb = ty;
-        const uint8_t* arow = &tile[nn * FT_LW + 16 * cb + 16 * g];
-        // Vertical: out(r, x) = sum_t tap(t) h(r + t, x) over the same K = 64 LDS rows, so those accumulators ARE an
-        // MFMA operand once split into bytes, h = 256 hi + lo (each byte as b - 128, like the pixels): K slot (g, j)
-        // of lane (n, g) is LDS row 16 (j >> 2) + 4 g + (j & 3) -- dword rb holds the four bytes of acc[rb][0 .. 3].
-        // K need not be in row order, the tap operand only has to use the same labelling.
-        dt_v4i Hlo, Hhi;
-#pragma unroll
-        for (int rb = 0; rb < 4; ++rb) {
-            const uint2 lo = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW);
-            const uint2 hi = *reinterpret_cast<const uint2*>(arow + 16 * rb * FT_LW + 8);
-            const dt_v4i A = {(int)(lo.x ^ 0x80808080u), (int)(lo.y ^ 0x80808080u), (int)(hi.x ^ 0x80808080u),
-                              (int)(hi.y ^ 0x80808080u)};
-            const dt_v4i acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(A, B, Z, 0, 0, 0);
-            // bytes 0 and 1 of the four accumulators, transposed: {lo0, lo1, hi0, hi1}, {lo2, lo3, hi2, hi3}
-            const uint32_t p01 = __builtin_amdgcn_perm((uint32_t)acc[1], (uint32_t)acc[0], 0x05010400u);
-            const uint32_t p23 = __builtin_amdgcn_perm((uint32_t)acc[3], (uint32_t)acc[2], 0x05010400u);
-            Hlo[rb] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
-            Hhi[rb] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
-        }
-        // The product is taken transposed, D[column][row] = H^T x T^T with H as A: lane (x, g) ends with output row
-        // 16 ob + x, columns 16 cb + 4 g .. + 3 as one dword.  The tap operand of output-row block ob: byte j of lane
-        // (x, g) is tap(row(g, j) - (16 ob + x)), so dword jj is the four taps from 16 (jj - ob) + 4 g - x
-        // = kh[x & 3][4 (jj - ob) + g - (x >> 2)], non-zero only for jj - ob in {0, 1}: two registers from s_band serve
-        // every ob.  Output row r reads LDS rows r .. r + 8 (all inside the 64 for the 56 stored rows), so every stored
-        // row sees all nine taps: sum = 256 (vh + 128 * 256) + (vl + 128 * 256), and the start value of vl carries
-        // both terms and 2^15, the rounding term of (sum + 2^15) >> 16.  The output byte is byte 2 (sum < 2^24).
-        const int T0 = (int)band[g], T1 = (int)band[g + 4];
-        const int cv = 257 * kw.hbias + (1 << 15);
-        const dt_v4i Cv = {cv, cv, cv, cv};
-        // The bytes go through the LDS the pretest list no longer needs, so that the global stores are whole 64-B row
-        // segments: row R's 16 dwords at s_share[16 R ..], the 16-B column groups XORed with (R >> 2) & 3 so that the
-        // 64 lanes of a store instruction (16 rows x 4 dwords) hit 64 different banks.
-        uint32_t* ostage = &s_share[nn * 16 + ((4 * cb) ^ (nn & 12)) + g];
-#pragma unroll
-        for (int ob = 0; ob < 4; ++ob) {
-            dt_v4i T = {0, 0, 0, 0};
-            T[ob] = T0;
-            if (ob < 3) T[ob + 1] = T1;
-            const dt_v4i vl = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hlo, T, Cv, 0, 0, 0);
-            const dt_v4i vh = __builtin_amdgcn_mfma_i32_16x16x64_i8(Hhi, T, Z, 0, 0, 0);
-            uint32_t v[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = ((uint32_t)vh[i] << 8) + (uint32_t)vl[i];
-            // two v_perm pick the byte 2s pairwise, one v_perm joins the pairs
-            ostage[ob * 16 * 16] = __builtin_amdgcn_perm(__builtin_amdgcn_perm(v[3], v[2], 0x0c0c0602u),
-                                                         __builtin_amdgcn_perm(v[1], v[0], 0x0c0c0602u), 0x05040100u);
-        }
-        __syncthreads();  // publishes s_base too
-        // 4 lanes per row, 16 B each; rows past the tile (the upper half of ob = 3) and past the image are not stored,
-        // columns past W land in the row padding
-        if (tid < FT_H * 4) {
-            const int R = tid >> 2, q = tid & 3;
-            const int bp = blur_pitch(W);
-            if (r0 + R < H)
-                *reinterpret_cast<uint4*>(blur + ((int64_t)img * H + r0 + R) * bp + c0 + 16 * (q ^ ((R >> 2) & 3))) =
-                    *reinterpret_cast<const uint4*>(&s_share[R * 16 + 4 * q]);
-        }
-        DP_MARK(3);
-        if (n > 0) harris(s_base);
-        DP_MARK(4);
-        DP_STORE();
-        return;
-    }
-    // No blur, or a tap above 127 (does not fit int8): the v_dot4 horizontal and v_dot2 vertical passes, h through LDS.
-    // One global atomic per workgroup reserves the output range of this tile's corners.
+    // One global atomic per workgroup reserves the output range of this tile's corners; it is issued first and its
+    // latency hides behind the blur.  The barrier publishes s_base and the blur's staged rows.
     if (tid == 0 && n > 0) s_base = atomicAdd(&cand_count[img], n);
-    if (kBlur) {
-        // horizontal pass, exact: h = sum_j k_j * p[x + j] as two v_dot4_u32_u8 + one mad on the byte row
-        // (rows start 4-byte aligned: FT_LW = 72).  h <= 255 * 256 fits 16 bits; rows 2q and 2q+1 are
-        // packed into one dword so the vertical pass can use v_dot2_u32_u16.  One item = 4 adjacent
-        // columns of a row pair: 3 LDS dwords per row feed all 4 outputs, one 16-B LDS store.
-        const uint32_t* trow = reinterpret_cast<const uint32_t*>(tile);
-        constexpr int kItems = (FT_LH / 2) * (FT_W / 4);
-        for (int i = tid; i < kItems; i += 256) {
-            const int q = i >> 4, xq = (i & 15) * 4;
-            uint32_t hv[2][4];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const uint32_t* wr = trow + ((2 * q + h) * FT_LW >> 2) + (xq >> 2);
-                const uint32_t d0 = wr[0], d1 = wr[1], d2 = wr[2];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    uint32_t acc = __builtin_amdgcn_udot4(d0, kw.kh[j][0], 0u, false);
-                    acc = __builtin_amdgcn_udot4(d1, kw.kh[j][1], acc, false);
-                    hv[h][j] = __builtin_amdgcn_udot4(d2, kw.kh[j][2], acc, false);
-                }
-            }
-            *reinterpret_cast<uint4*>(&hbuf[q * FT_W + xq]) =
-                make_uint4(hv[0][0] | (hv[1][0] << 16), hv[0][1] | (hv[1][1] << 16), hv[0][2] | (hv[1][2] << 16),
-                           hv[0][3] | (hv[1][3] << 16));
-        }
-    }
+    if constexpr (kBlur) blur_tile_mfma(tile, s_band, s_share, kw.hbias, lane, ty);
     __syncthreads();
+    if constexpr (kBlur) blur_store_rows(s_share, blur, img, H, W, r0, c0, tid);
     DP_MARK(3);
     if (n > 0) harris(s_base);
     DP_MARK(4);
-    if (kBlur) {
-        // vertical pass, exact u32: rows 2m and 2m+1 of columns xq..xq+3 from the row-pair dwords P_m .. P_{m+4}
-        // (one 16-B LDS read per row pair); each row's 4 bytes go out as one dword store, so 16 lanes write a
-        // tile row's 64-B segment of the 128-B aligned pitched image (columns past W land in the row padding)
-        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
-        const int bp = blur_pitch(W);
-        uint8_t* dst = blur + (int64_t)img * H * bp;
-        for (int i = tid; i < (FT_H / 2) * (FT_W / 4); i += 256) {
-            const int m = i >> 4, xq = (i & 15) * 4;
-            uint4 P[5];
-#pragma unroll
-            for (int t = 0; t < 5; ++t) {
-                // one ds_read_b128 per row pair: 16 lanes cover a row pair's 64 dwords (every bank once).  The
-                // volatile access keeps it whole: otherwise the compiler splits it into ds_read2_b32 pairs at a
-                // 4-dword lane stride, 4-way bank conflicts (SQ_LDS_BANK_CONFLICT ~240 cycles per wave, r03 counters)
-                typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-                typedef const volatile __attribute__((address_space(3))) u32x4 lds_u32x4;
-                const u32x4 q = *(lds_u32x4*)(&s_share[(m + t) * FT_W + xq]);
-                P[t] = make_uint4(q.x, q.y, q.z, q.w);
-            }
-            // accumulators start at 2^15 (the rounding term of (acc + 2^15) >> 16)
-            uint32_t ev[4], od[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                auto col = [&](const uint4& q) { return j == 0 ? q.x : j == 1 ? q.y : j == 2 ? q.z : q.w; };
-                uint32_t e = 1u << 15, o = 1u << 15;
-#pragma unroll
-                for (int t = 0; t < 5; ++t) {
-                    e = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, col(P[t])), __builtin_bit_cast(us2, kw.kve[t]), e, false);
-                    o = __builtin_amdgcn_udot2(__builtin_bit_cast(us2, col(P[t])), __builtin_bit_cast(us2, kw.kvo[t]), o, false);
-                }
-                ev[j] = e;
-                od[j] = o;
-            }
-            uint32_t w0, w1;
-            if (kw.byte2) {
-                // output byte = byte 2 of each accumulator: two v_perm pick them pairwise, one v_perm joins the pairs
-                w0 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(ev[3], ev[2], 0x0c0c0602u),
-                                           __builtin_amdgcn_perm(ev[1], ev[0], 0x0c0c0602u), 0x05040100u);
-                w1 = __builtin_amdgcn_perm(__builtin_amdgcn_perm(od[3], od[2], 0x0c0c0602u),
-                                           __builtin_amdgcn_perm(od[1], od[0], 0x0c0c0602u), 0x05040100u);
-            } else {
-                w0 = w1 = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    w0 |= min(ev[j] >> 16, 255u) << (8 * j);
-                    w1 |= min(od[j] >> 16, 255u) << (8 * j);
-                }
-            }
-            const int r = r0 + 2 * m, c = c0 + xq;
-            if (r < H) *reinterpret_cast<uint32_t*>(&dst[(int64_t)r * bp + c]) = w0;
-            if (r + 1 < H) *reinterpret_cast<uint32_t*>(&dst[(int64_t)(r + 1) * bp + c]) = w1;
-        }
-    }
-    DP_MARK(5);
     DP_STORE();
 }
 
@@ -711,6 +612,15 @@ void launch_fast_harris(const uint8_t* imgs, int n_images, int H, int W, int str
 void launch_detect_blur(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch, int thr,
                         int eig, uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, const uint16_t* k9_host,
                         uint8_t* blur, hipStream_t s) {
+    // the fused blur takes the taps as int8 (yv_set_blur_kernel has checked that they sum to 256); a tap above 127
+    // takes the detector without blur and the stand-alone blur, which reads the image a second time
+    uint32_t max_tap = 0;
+    for (int i = 0; i < 9; ++i) max_tap = k9_host[i] > max_tap ? k9_host[i] : max_tap;
+    if (max_tap > 127) {
+        launch_fast_harris(imgs, n_images, H, W, stride, pitch, thr, eig, cand_keys, cap, cand_count, s);
+        launch_blur9(imgs, n_images, H, W, stride, pitch, k9_host, blur, s);
+        return;
+    }
     dim3 grid(((W + FT_W - 1) / FT_W) * ((H + FT_H - 1) / FT_H) * n_images);
     const K9 kw = make_k9(k9_host);
     hipLaunchKernelGGL(detect_kernel<true>, grid, dim3(256), 0, s, imgs, H, W, stride, pitch, thr, eig, cand_keys, cap,
@@ -764,8 +674,14 @@ __global__ __launch_bounds__(256) void blur9_kernel(const uint8_t* __restrict__ 
 void launch_blur9(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch,
                   const uint16_t* k9_host, uint8_t* blur, hipStream_t s) {
     const K9 kw = make_k9(k9_host);
-    dim3 grid((W + BL_W - 1) / BL_W, (H + BL_H - 1) / BL_H, n_images);
-    hipLaunchKernelGGL(blur9_kernel, grid, dim3(256), 0, s, imgs, H, W, stride, pitch, kw, blur);
+    // the image index is blockIdx.z, which ends at 65,535: a larger batch goes in slices
+    constexpr int kMaxGridZ = 65535;
+    for (int i0 = 0; i0 < n_images; i0 += kMaxGridZ) {
+        const int n = n_images - i0 < kMaxGridZ ? n_images - i0 : kMaxGridZ;
+        dim3 grid((W + BL_W - 1) / BL_W, (H + BL_H - 1) / BL_H, n);
+        hipLaunchKernelGGL(blur9_kernel, grid, dim3(256), 0, s, imgs + (int64_t)i0 * pitch, H, W, stride, pitch, kw,
+                           blur + (int64_t)i0 * blur_image_bytes(H, W));
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
