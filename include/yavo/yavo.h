@@ -50,10 +50,10 @@ int yv_create(int device, yv_ctx** out);
 void yv_destroy(yv_ctx* ctx);
 /* The stream all yv_* calls on this context use (hipStream_t as void*). */
 void* yv_stream(yv_ctx* ctx);
-/* Block until all work queued on the context stream has finished. */
 /* A second stream of the context on a hardware queue of its own (never the context stream's), made on first use and
  * kept until yv_destroy: work issued on it overlaps the context stream's (the sequence's BA windows). */
 void* yv_side_stream(yv_ctx* ctx);
+/* Block until all work queued on the context stream has finished. */
 int yv_sync(yv_ctx* ctx);
 /* Synchronous copies between host memory and device memory (e.g. a yv_batch_view array) on the
  * context stream. */
@@ -101,6 +101,29 @@ int yv_match_features(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoi
 /* Brief::removeOutliers (src/BriefDescriptor.cc:213-231; include/BriefDescriptor.hpp:64). */
 int yv_filter_matches(yv_ctx* ctx, const yv_match* in, int n, int thr, yv_match* out, int* n_out);
 
+/* ---- 2-NN matching: Lowe's ratio test and the mutual cross-check (beyond the reference; exact, all integer) ---- */
+/* With d(i, j) the Hamming distance of query i and train point j:
+ *   (d1, j1)(i) = the lexicographic minimum of (d(i, j), j) over j -- what yv_match_features returns;
+ *   (d2, j2)(i) = the same minimum over j != j1(i): d2 >= d1, and on d2 == d1 j2 is the next tied index;
+ *   nt < 2: d2 = INT32_MAX, j2 = -1; nt == 0: also d1 = INT32_MAX, j1 = -1;
+ *   i1(j)       = the smallest query index that minimises d(i, j) (-1 for nq == 0).
+ * YV_MATCH_RATIO keeps a query iff (int64)d1 * ratio_den < (int64)d2 * ratio_num (0 < num <= den <= 32768: an exact
+ * tie d1 == d2 never passes); YV_MATCH_MUTUAL iff j1(i) >= 0 and i1(j1(i)) == i.  Both are applied on top of
+ * removeOutliers' limit, which stays the one over all queries of the pair. */
+#define YV_MATCH_RATIO 1
+#define YV_MATCH_MUTUAL 2
+typedef struct yv_match2 { int32_t d1, j1, d2, j2; } yv_match2; /* 16 B */
+/* The two nearest train points of every query (out capacity nq) and, with rev != NULL (capacity nt), every train
+ * point's best query i1(j).  YV_ERR_CAPACITY for nq or nt above 4096.  Both calls check their arguments before the
+ * context; on a machine without a GPU (where no context can exist) a NULL context then yields YV_ERR_NODEVICE. */
+int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, yv_match2* out,
+                  int32_t* rev);
+/* yv_match_features + yv_filter_matches(thr) + the tests selected by flags, in query order with matched = true (flags
+ * = 0: exactly those two calls).  out capacity nq; keep (may be NULL, capacity nq) = one byte per query.
+ * YV_ERR_INVALID for flags outside 0..3 or, with YV_MATCH_RATIO, a ratio outside 0 < num <= den <= 32768. */
+int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags,
+                    int ratio_num, int ratio_den, yv_match* out, int* n_out, uint8_t* keep);
+
 /* ---- batched device pipeline (inputs resident in HBM) ---------------------------------------------- */
 /* A batch owns device workspace for up to max_images images of H x W and max_pairs match pairs.  Slot
  * index max_images is the "carry" slot: it holds the keypoints / descriptors of one image of the
@@ -119,6 +142,21 @@ int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs /* [2*n_pairs] */, int 
  * src/LoopHandler.cc:192,537). */
 int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride, int64_t image_pitch,
                  int match_thr, int carry_from, void* stream);
+/* The match filter of the following runs: flags = 0 (the default) is the reference's behaviour, YV_MATCH_RATIO and /
+ * or YV_MATCH_MUTUAL add the tests above.  With a filter on, yv_batch_run runs the top-2 matcher, the matcher on the
+ * swapped pairs (YV_MATCH_MUTUAL only) and a finalize that writes `matches`, `match_dj` and `match_lim` as before,
+ * `filtered` / `filt_count` with the kept records only, and the arrays of yv_batch_match2_view; yv_batch_track,
+ * yv_batch_track_map and the LK mode then use only kept matches.  The extra device buffers are allocated by the
+ * first call with flags != 0.  Same argument checks as yv_match_robust. */
+int yv_batch_set_match_filter(yv_batch* b, int flags, int ratio_num, int ratio_den);
+typedef struct yv_batch_match2_view {
+    const yv_match2* nn2;             /* [max_pairs][max_kp] */
+    const int32_t* rev;               /* [max_pairs][max_kp]: i1(j); -1 everywhere without YV_MATCH_MUTUAL */
+    const uint8_t* keep;              /* [max_pairs][max_kp] */
+} yv_batch_match2_view;
+/* Device views of the filter's arrays (the last run with a filter on); YV_ERR_INVALID before the filter was ever
+ * switched on. */
+int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v);
 /* Tracking (PnP) over the last run's matches: track t = {stereo_pair, temporal_pair} (pair indices of
  * yv_batch_set_pairs) where the stereo pair's query image (frame k left) is the temporal pair's train
  * image.  Each frame-(k-1) keypoint kept by removeOutliers in the temporal pair whose frame-k keypoint is
@@ -154,8 +192,8 @@ int yv_batch_set_track_lk(yv_batch* b, int image_step, int win, int max_level, i
                           double min_eig);
 /* Per-stage device time of the runs since the last reset, when timing is enabled (HIP events recorded
  * on the run stream around every stage).  Stages: 0 detect (FAST + Harris + blur, one fused kernel),
- * 1 top-K + checkBoundry, 2 BRIEF, 3 match, 4 Matches records + removeOutliers (+ carry copies),
- * 5 track edges (stereo triangulation), 6 track poses (LM).  ms[i] = summed milliseconds, *n_runs = runs
+ * 1 top-K + checkBoundry, 2 BRIEF, 3 match (with a match filter: both matcher launches), 4 Matches records +
+ * removeOutliers (+ carry copies, + the match filter's tests), 5 track edges (stereo triangulation), 6 track poses (LM).  ms[i] = summed milliseconds, *n_runs = runs
  * accumulated (stages 5-6 summed over the runs followed by yv_batch_track).  on = 2: events around the
  * detect kernel only (ms[0]; the other stages read 0) -- two events per run instead of nine. */
 int yv_batch_enable_timing(yv_batch* b, int on);

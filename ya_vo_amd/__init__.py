@@ -31,6 +31,10 @@ KEYPOINT_DTYPE = np.dtype([("x", "<i4"), ("y", "<i4"), ("id", "<i4"), ("matched"
                            ("featVec", "u1", (32,)), ("_pad", "u1", (3,))])
 MATCH_DTYPE = np.dtype([("pt1", KEYPOINT_DTYPE), ("pt2", KEYPOINT_DTYPE), ("distance", "<i4")])
 assert KEYPOINT_DTYPE.itemsize == 48 and MATCH_DTYPE.itemsize == 100
+# yv_match2: the nearest and second nearest train point of a query (distance, index; INT32_MAX / -1: none)
+MATCH2_DTYPE = np.dtype([("d1", "<i4"), ("j1", "<i4"), ("d2", "<i4"), ("j2", "<i4")])
+YV_MATCH_RATIO = 1
+YV_MATCH_MUTUAL = 2
 
 # cv::GaussianBlur(Size(9, 9), 2.5) 8U fixed-point kernel (src/BriefDescriptor.cc:90)
 DEFAULT_BLUR_KERNEL = np.array([12, 22, 31, 41, 44, 41, 31, 22, 12], dtype=np.uint16)
@@ -53,6 +57,10 @@ class _BatchView(ctypes.Structure):
                 ("edge_count", ctypes.c_void_p), ("edge_X", ctypes.c_void_p), ("edge_uv", ctypes.c_void_p),
                 ("edge_query", ctypes.c_void_p), ("edge_outlier", ctypes.c_void_p),
                 ("track_inliers", ctypes.c_void_p), ("blur_pitch", ctypes.c_int)]
+
+
+class _BatchMatch2View(ctypes.Structure):
+    _fields_ = [("nn2", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("keep", ctypes.c_void_p)]
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -83,6 +91,10 @@ SIGNATURES = {
     "yv_describe": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, ctypes.POINTER(_I)]),
     "yv_match_features": (_I, [_P, _P, _I, _P, _I, _P]),
     "yv_filter_matches": (_I, [_P, _P, _I, _I, _P, ctypes.POINTER(_I)]),
+    "yv_match_knn2": (_I, [_P, _P, _I, _P, _I, _P, _P]),
+    "yv_match_robust": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I), _P]),
+    "yv_batch_set_match_filter": (_I, [_P, _I, _I, _I]),
+    "yv_batch_match2_view_get": (_I, [_P, ctypes.POINTER(_BatchMatch2View)]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -481,7 +493,36 @@ class Context(_GeomMixin):
                "yv_filter_matches")
         return out[:n.value].copy()
 
+    def match_knn2(self, q: np.ndarray, t: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """yv_match_knn2 -> (nn2 [nq] MATCH2_DTYPE, rev [nt] int32: every train point's best query, -1: none)."""
+        q = np.ascontiguousarray(q, dtype=KEYPOINT_DTYPE)
+        t = np.ascontiguousarray(t, dtype=KEYPOINT_DTYPE)
+        nn2 = np.zeros(max(len(q), 1), MATCH2_DTYPE)
+        rev = np.zeros(max(len(t), 1), np.int32)
+        _check(self.lib.yv_match_knn2(self.handle, _ptr(q), len(q), _ptr(t), len(t), _ptr(nn2), _ptr(rev)),
+               "yv_match_knn2")
+        return nn2[:len(q)].copy(), rev[:len(t)].copy()
 
+    def match_robust(self, q: np.ndarray, t: np.ndarray, thr: int = 20, ratio=(4, 5),
+                     mutual: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+        """yv_match_robust: matchFeatures + removeOutliers(thr) + Lowe's ratio test d1 * den < d2 * num (ratio =
+        (num, den), None: off) + the mutual cross-check -> (filtered MATCH_DTYPE array, keep [nq] bool)."""
+        q = np.ascontiguousarray(q, dtype=KEYPOINT_DTYPE)
+        t = np.ascontiguousarray(t, dtype=KEYPOINT_DTYPE)
+        flags, num, den = _match_filter_args(ratio, mutual)
+        out = np.zeros(max(len(q), 1), MATCH_DTYPE)
+        keep = np.zeros(max(len(q), 1), np.uint8)
+        n = ctypes.c_int()
+        _check(self.lib.yv_match_robust(self.handle, _ptr(q), len(q), _ptr(t), len(t), thr, flags, num, den, _ptr(out),
+                                        ctypes.byref(n), _ptr(keep)), "yv_match_robust")
+        return out[:n.value].copy(), keep[:len(q)].astype(bool)
+
+
+def _match_filter_args(ratio, mutual) -> Tuple[int, int, int]:
+    """(flags, ratio_num, ratio_den) of yv_match_robust / yv_batch_set_match_filter."""
+    flags = (YV_MATCH_RATIO if ratio is not None else 0) | (YV_MATCH_MUTUAL if mutual else 0)
+    num, den = (int(ratio[0]), int(ratio[1])) if ratio is not None else (0, 1)
+    return flags, num, den
 
 
 class Batch:
@@ -576,6 +617,19 @@ class Batch:
     def view(self) -> _BatchView:
         v = _BatchView()
         _check(self.lib.yv_batch_view_get(self.handle, ctypes.byref(v)), "yv_batch_view_get")
+        return v
+
+    def set_match_filter(self, ratio=None, mutual: bool = False) -> None:
+        """The match filter of the following runs (yv_batch_set_match_filter): ratio = (num, den) switches Lowe's
+        ratio test on, mutual the cross-check; both off (the default) is the reference's behaviour."""
+        flags, num, den = _match_filter_args(ratio, mutual)
+        _check(self.lib.yv_batch_set_match_filter(self.handle, flags, num, den), "yv_batch_set_match_filter")
+
+    def match2_view(self) -> _BatchMatch2View:
+        """Device arrays of the match filter (yv_batch_match2_view_get): nn2 [max_pairs][max_kp] MATCH2_DTYPE, rev
+        [max_pairs][max_kp] int32, keep [max_pairs][max_kp] uint8."""
+        v = _BatchMatch2View()
+        _check(self.lib.yv_batch_match2_view_get(self.handle, ctypes.byref(v)), "yv_batch_match2_view_get")
         return v
 
 

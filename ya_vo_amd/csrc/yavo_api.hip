@@ -100,6 +100,16 @@ struct yv_batch {
     int32_t* filt_count = nullptr;
     int2* match_dj = nullptr;       // [max_pairs][max_kp] {distance, train index}
     int32_t* match_lim = nullptr;   // [max_pairs] removeOutliers limit
+    // the match filter (yv_batch_set_match_filter): allocated by the first call that switches it on
+    int match_flags = 0, ratio_num = 0, ratio_den = 1;
+    int run_flags = 0;              // the filter of the last yv_batch_run (0: the tracks read no keep array)
+    bool m2_alloc = false;
+    uint32_t* match_key2 = nullptr; // [max_pairs][max_kp] second-best keys
+    uint32_t* rev_key = nullptr;    // [max_pairs][max_kp] the swapped pairs' keys
+    int32_t* pairs_rev = nullptr;   // [max_pairs][2] {train image, query image}
+    int4* nn2 = nullptr;            // [max_pairs][max_kp] {d1, j1, d2, j2}
+    int32_t* rev = nullptr;         // [max_pairs][max_kp]
+    uint8_t* keep = nullptr;        // [max_pairs][max_kp]
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)
@@ -232,7 +242,8 @@ void batch_free(yv_batch* b) {
                     b->brief_loff, b->kp_count,  b->kp_count_build, b->keypoints,  b->desc, b->blur,   b->pairs,     b->match_key,
                     b->matches,   b->match_count, b->filtered, b->filt_count, b->staging,  b->match_dj,
                     b->match_lim, b->tracks,     b->track_K,  b->T_right,    b->edge_X,    b->edge_uv,
-                    b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers};
+                    b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers,
+                    b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep};
     if (b->bstream) (void)hipStreamSynchronize(b->bstream);
     if (b->side) (void)hipStreamSynchronize(b->side);
     for (void* p : ptrs)
@@ -367,6 +378,53 @@ int ensure_single(yv_ctx* ctx, int H, int W) {
     }
     ctx->single = b;
     return YV_OK;
+}
+
+static_assert(YV_MATCH_RATIO == yavo::kMatchRatio && YV_MATCH_MUTUAL == yavo::kMatchMutual, "yavo.h / yavo_internal.h");
+static_assert(sizeof(yv_match2) == sizeof(int4), "nn2 is written as int4 {d1, j1, d2, j2}");
+
+// 0 <= flags <= 3 and, with the ratio test, 0 < num <= den <= 32768 (d * den and d * num stay far inside int64, and
+// num <= den makes a tie d1 == d2 fail)
+bool match_filter_args_ok(int flags, int num, int den) {
+    if (flags < 0 || flags > (YV_MATCH_RATIO | YV_MATCH_MUTUAL)) return false;
+    if ((flags & YV_MATCH_RATIO) && !(num > 0 && num <= den && den <= 32768)) return false;
+    return true;
+}
+
+// the swapped pair list of the reverse match
+int upload_pairs_rev(yv_batch* b) {
+    if (!b->m2_alloc || b->n_pairs <= 0) return YV_OK;
+    std::vector<int32_t> r(b->h_pairs.size());
+    for (size_t i = 0; i + 1 < r.size(); i += 2) {
+        r[i] = b->h_pairs[i + 1];
+        r[i + 1] = b->h_pairs[i];
+    }
+    YV_HIP(hipMemcpyAsync(b->pairs_rev, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    return YV_OK;
+}
+
+// the match filter's device buffers, on first use
+int ensure_match2(yv_batch* b) {
+    if (b->m2_alloc) return YV_OK;
+    const size_t nk = (size_t)b->max_kp, np = (size_t)std::max(b->max_pairs, 1);
+    int rc = YV_OK;
+    rc |= dalloc(&b->match_key2, np * nk);
+    rc |= dalloc(&b->rev_key, np * nk);
+    rc |= dalloc(&b->pairs_rev, np * 2);
+    rc |= dalloc(&b->nn2, np * nk);
+    rc |= dalloc(&b->rev, np * nk);
+    rc |= dalloc(&b->keep, np * nk);
+    if (rc != YV_OK) return YV_ERR_HIP;  // batch_free releases what was allocated
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipMemsetAsync(b->match_key2, 0xFF, np * nk * sizeof(uint32_t), s));
+    YV_HIP(hipMemsetAsync(b->rev_key, 0xFF, np * nk * sizeof(uint32_t), s));
+    YV_HIP(hipMemsetAsync(b->nn2, 0, np * nk * sizeof(int4), s));
+    YV_HIP(hipMemsetAsync(b->rev, 0xFF, np * nk * sizeof(int32_t), s));
+    YV_HIP(hipMemsetAsync(b->keep, 0, np * nk, s));
+    YV_HIP(hipStreamSynchronize(s));
+    b->m2_alloc = true;
+    return upload_pairs_rev(b);
 }
 
 int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
@@ -652,6 +710,27 @@ int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs, int n_pairs) {
     b->h_pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
     b->n_pairs = n_pairs;
     b->n_tracks = 0;  // tracks refer to pair indices: set them again
+    return upload_pairs_rev(b);
+}
+
+int yv_batch_set_match_filter(yv_batch* b, int flags, int ratio_num, int ratio_den) {
+    if (!match_filter_args_ok(flags, ratio_num, ratio_den) || !b) return YV_ERR_INVALID;
+    if (flags != 0) {
+        if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+        const int rc = ensure_match2(b);
+        if (rc != YV_OK) return rc;
+    }
+    b->match_flags = flags;
+    b->ratio_num = (flags & YV_MATCH_RATIO) ? ratio_num : 0;
+    b->ratio_den = (flags & YV_MATCH_RATIO) ? ratio_den : 1;
+    return YV_OK;
+}
+
+int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v) {
+    if (!b || !v || !b->m2_alloc) return YV_ERR_INVALID;
+    v->nn2 = reinterpret_cast<const yv_match2*>(b->nn2);
+    v->rev = b->rev;
+    v->keep = b->keep;
     return YV_OK;
 }
 
@@ -749,20 +828,31 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
                        b->desc, b->brief_loff, new_loff, s);
     rc |= record_stage(b, s, run, 3);
     if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
-    if (b->n_pairs > 0) {
+    b->run_flags = b->n_pairs > 0 ? b->match_flags : 0;
+    // the asynchronous edge build reads a copy of the keypoint counts (the next run's top-K rewrites them):
+    // the finalize kernel writes it, where a separate device copy waited ~50 us for a CU at the end of the step
+    const bool copy_counts = b->n_pairs > 0 && b->overlap && b->build_async && b->lk_step == 0;
+    if (b->run_flags != 0) {
+        // the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
+        yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, b->match_key2, s);
+        if (b->match_flags & YV_MATCH_MUTUAL)
+            yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, b->n_pairs, K, K, b->rev_key, s);
+        rc |= record_stage(b, s, run, 4);
+        yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs,
+                                           b->n_pairs, K, match_thr, b->match_flags, b->ratio_num, b->ratio_den,
+                                           b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj,
+                                           b->match_lim, b->nn2, b->rev, b->keep, s,
+                                           copy_counts ? b->kp_count_build : nullptr, b->nslots);
+    } else if (b->n_pairs > 0) {
         yavo::launch_match(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, s);
         rc |= record_stage(b, s, run, 4);
-        // the asynchronous edge build reads a copy of the keypoint counts (the next run's top-K rewrites them):
-        // the finalize kernel writes it, where a separate device copy waited ~50 us for a CU at the end of the step
-        const bool copy_counts = b->overlap && b->build_async && b->lk_step == 0;
         yavo::launch_match_finalize(b->match_key, b->keypoints, b->kp_count, b->pairs, b->n_pairs, K, match_thr,
                                     b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj,
                                     b->match_lim, s, copy_counts ? b->kp_count_build : nullptr, b->nslots);
-        b->counts_copied = copy_counts;
     } else {
         rc |= record_stage(b, s, run, 4);
-        b->counts_copied = false;
     }
+    b->counts_copied = copy_counts;
     rc |= record_stage(b, s, run, 5);
     if (rc != YV_OK) return YV_ERR_HIP;
     // The carry slot keeps this run's frame k-1 (the query of its first temporal pair) until the next run
@@ -1034,7 +1124,8 @@ int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stre
         if (b->lk_ev_pending[lk_j]) YV_HIP(hipStreamWaitEvent(s_run, b->ev_lk[lk_j], 0));
         b->lk_ev_pending[lk_j] = false;
         yavo::launch_stereo_points(b->lk_sp, b->n_tracks, b->pairs, b->keypoints, b->kp_count, b->match_dj,
-                                   b->match_lim, b->max_kp, b->track_K, b->T_right, lkX, lkP, lkQ, lkC, s_run);
+                                   b->match_lim, b->max_kp, b->track_K, b->T_right, lkX, lkP, lkQ, lkC, s_run,
+                                   b->run_flags ? b->keep : nullptr);
     }
     const int32_t* build_counts = b->kp_count;
     if (b->overlap && b->build_async) {
@@ -1069,7 +1160,8 @@ int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stre
         }
     } else {
         yavo::launch_track_build(b->tracks, b->n_tracks, b->pairs, b->keypoints, build_counts, b->match_dj,
-                                 b->match_lim, b->max_kp, b->track_K, b->T_right, eX, euv, eq, ec, s);
+                                 b->match_lim, b->max_kp, b->track_K, b->T_right, eX, euv, eq, ec, s,
+                                 b->run_flags ? b->keep : nullptr);
     }
     if (b->overlap) YV_HIP(hipEventRecord(b->ev_edges[k], s));
     if (s != s_run && b->lk_step == 0) {  // (the LK stage reads nothing the next run writes: no join)
@@ -1283,6 +1375,83 @@ int yv_filter_matches(yv_ctx* ctx, const yv_match* in, int n, int thr, yv_match*
     yavo::launch_filter_records(b->matches, n, thr, b->filtered, b->filt_count, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->filt_count, sizeof(int32_t), s));
+    YV_HIP(stage_sync(ctx, s));
+    const int m = ctx->h_pinned[0];
+    if (m > 0) {
+        YV_HIP(stage_d2h(ctx, out, b->filtered, sizeof(yv_match) * (size_t)m, s));
+        YV_HIP(stage_sync(ctx, s));
+    }
+    *n_out = m;
+    return YV_OK;
+}
+
+namespace {
+// uploads both keypoint lists into the single-image workspace (query = slot 0, train = slot 1), packs their
+// descriptors and runs the filtered match of its one pair
+int match2_single(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags, int num,
+                  int den, bool with_rev, hipStream_t s) {
+    int st = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    st = ensure_match2(b);
+    if (st != YV_OK) return st;
+    const size_t nk = (size_t)b->max_kp;
+    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
+    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + nk, t, sizeof(yv_keypoint) * (size_t)nt, s));
+    ctx->h_pinned[0] = nq;
+    ctx->h_pinned[1] = nt;
+    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
+    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
+    yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, 1, b->max_kp, nt, b->match_key, b->match_key2, s);
+    if (with_rev) yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, 1, b->max_kp, nq, b->rev_key, s);
+    yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs, 1,
+                                       b->max_kp, thr, flags, num, den, b->matches, b->match_count, b->filtered,
+                                       b->filt_count, b->match_dj, b->match_lim, b->nn2, b->rev, b->keep, s);
+    return check_launch();
+}
+}  // namespace
+
+int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, yv_match2* out,
+                  int32_t* rev) {
+    if (nq < 0 || nt < 0 || (nq > 0 && (!q || !out)) || (nt > 0 && !t)) return YV_ERR_INVALID;
+    if (nq > yavo::kMaxKp || nt > yavo::kMaxKp) return YV_ERR_CAPACITY;
+    if (!ctx) return yv_device_count() > 0 ? YV_ERR_INVALID : YV_ERR_NODEVICE;
+    if (nq == 0) {
+        if (rev)
+            for (int j = 0; j < nt; ++j) rev[j] = -1;  // no query
+        return YV_OK;
+    }
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = ctx->stream;
+    const int st = match2_single(ctx, q, nq, t, nt, 0, 0, 0, 1, rev != nullptr, s);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    YV_HIP(stage_d2h(ctx, out, b->nn2, sizeof(yv_match2) * (size_t)nq, s));
+    if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, b->rev, sizeof(int32_t) * (size_t)nt, s));
+    YV_HIP(stage_sync(ctx, s));
+    return YV_OK;
+}
+
+int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags,
+                    int ratio_num, int ratio_den, yv_match* out, int* n_out, uint8_t* keep) {
+    if (!match_filter_args_ok(flags, ratio_num, ratio_den) || !n_out || nq < 0 || nt < 0 ||
+        (nq > 0 && (!q || !out)) || (nt > 0 && !t))
+        return YV_ERR_INVALID;
+    if (nq > yavo::kMaxKp || nt > yavo::kMaxKp) return YV_ERR_CAPACITY;
+    if (!ctx) return yv_device_count() > 0 ? YV_ERR_INVALID : YV_ERR_NODEVICE;
+    *n_out = 0;
+    if (nq == 0) return YV_OK;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = ctx->stream;
+    const bool ratio = (flags & YV_MATCH_RATIO) != 0;
+    const int st = match2_single(ctx, q, nq, t, nt, thr, flags, ratio ? ratio_num : 0, ratio ? ratio_den : 1,
+                                 (flags & YV_MATCH_MUTUAL) != 0, s);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->filt_count, sizeof(int32_t), s));
+    if (keep) YV_HIP(stage_d2h(ctx, keep, b->keep, (size_t)nq, s));
     YV_HIP(stage_sync(ctx, s));
     const int m = ctx->h_pinned[0];
     if (m > 0) {

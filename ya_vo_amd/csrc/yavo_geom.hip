@@ -1435,12 +1435,14 @@ __global__ __launch_bounds__(NT) YAVO_LM_ATTR void pose_lm_kernel(const int32_t*
 // right camera at T_right; accepted iff triangulation succeeds and Z > 0 (triangulate2View,
 // src/LoopHandler.cc:658-726).  uv = (kp_{k-1}[i].x, kp_{k-1}[i].y) (the reference's measurement,
 // src/LoopHandler.cc:786).  Edges keep temporal query order.  One workgroup per track.
-template <int NT>
+// KEEP (the match filter is on): a temporal match i counts only if keep[tp][i], its stereo match only if keep[sp][j].
+template <int NT, bool KEEP>
 __global__ __launch_bounds__(NT) void track_build_kernel(
     const int32_t* __restrict__ tracks, const int32_t* __restrict__ pairs, const yv_keypoint* __restrict__ keypoints,
     const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj, const int32_t* __restrict__ match_lim,
     int max_kp, const double* __restrict__ Kall, const double* __restrict__ T_right, double* __restrict__ edge_X,
-    double* __restrict__ edge_uv, int32_t* __restrict__ edge_query, int32_t* __restrict__ edge_count) {
+    double* __restrict__ edge_uv, int32_t* __restrict__ edge_query, int32_t* __restrict__ edge_count,
+    const uint8_t* __restrict__ keep) {
     __shared__ int s_tmp[40];
     __shared__ double s_K[9], s_Ta[7], s_Tb[7];
     const int t = blockIdx.x, tid = threadIdx.x;
@@ -1470,9 +1472,13 @@ __global__ __launch_bounds__(NT) void track_build_kernel(
         double X[3];
         if (i < nq) {
             const int2 a = dj_t[i];
-            if (a.x < lim_t && a.y >= 0) {
+            bool kt = true;
+            if constexpr (KEEP) kt = keep[(int64_t)tp * max_kp + i] != 0;
+            if (a.x < lim_t && a.y >= 0 && kt) {
                 const int2 b = dj_s[a.y];
-                if (b.x < lim_s && b.y >= 0)
+                bool ks = true;
+                if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + a.y] != 0;
+                if (b.x < lim_s && b.y >= 0 && ks)
                     good = triangulate_px(kl[a.y].x, kl[a.y].y, kr[b.y].x, kr[b.y].y, s_Ta, s_Tb, s_K, X);
             }
         }
@@ -1496,13 +1502,13 @@ __global__ __launch_bounds__(NT) void track_build_kernel(
 // left keypoints whose stereo match (pair sp) survives removeOutliers and triangulates (left camera = world).
 // Compacted in keypoint order: X, the LK start point (x = column, y = row as cv::Point2f, :344) and the
 // keypoint index.  One workgroup per track.
-template <int NT>
+template <int NT, bool KEEP>
 __global__ __launch_bounds__(NT) void stereo_points_kernel(
     const int32_t* __restrict__ stereo_pairs, const int32_t* __restrict__ pairs,
     const yv_keypoint* __restrict__ keypoints, const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj,
     const int32_t* __restrict__ match_lim, int max_kp, const double* __restrict__ Kall,
     const double* __restrict__ T_right, double* __restrict__ pX, float* __restrict__ pts, int32_t* __restrict__ pq,
-    int32_t* __restrict__ pcount) {
+    int32_t* __restrict__ pcount, const uint8_t* __restrict__ keep) {
     __shared__ int s_tmp[40];
     __shared__ double s_K[9], s_Ta[7], s_Tb[7];
     const int t = blockIdx.x, tid = threadIdx.x;
@@ -1529,7 +1535,9 @@ __global__ __launch_bounds__(NT) void stereo_points_kernel(
         double X[3];
         if (j < nq) {
             const int2 a = dj[j];
-            if (a.x < lim && a.y >= 0) good = triangulate_px(kl[j].x, kl[j].y, kr[a.y].x, kr[a.y].y, s_Ta, s_Tb, s_K, X);
+            bool ks = true;
+            if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + j] != 0;
+            if (a.x < lim && a.y >= 0 && ks) good = triangulate_px(kl[j].x, kl[j].y, kr[a.y].x, kr[a.y].y, s_Ta, s_Tb, s_K, X);
         }
         int tot = 0;
         const int off = block_excl_scan_geom<NT>(good ? 1 : 0, s_tmp, &tot);
@@ -1735,22 +1743,34 @@ void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, con
 void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
                         const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
                         const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s) {
+                        int32_t* edge_count, hipStream_t s, const uint8_t* keep) {
     if (n_tracks <= 0) return;
     // 1024 threads: about one query keypoint per thread (the FP64 triangulations are latency-bound; 256 / 512 were
     // measured)
-    hipLaunchKernelGGL(geom::track_build_kernel<1024>, dim3(n_tracks), dim3(1024), 0, s, tracks, pairs, keypoints,
-                       kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv, edge_query, edge_count);
+    if (keep)
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, true>), dim3(n_tracks), dim3(1024), 0, s, tracks, pairs,
+                           keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv, edge_query,
+                           edge_count, keep);
+    else
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, false>), dim3(n_tracks), dim3(1024), 0, s, tracks, pairs,
+                           keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv, edge_query,
+                           edge_count, keep);
 }
 
 void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
                           const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
                           const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s) {
+                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep) {
     if (n_tracks <= 0) return;
     // 1024 threads: about one keypoint per thread (FP64 triangulations, latency-bound)
-    hipLaunchKernelGGL(geom::stereo_points_kernel<1024>, dim3(n_tracks), dim3(1024), 0, s, stereo_pairs, pairs,
-                       keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts, pq, pcount);
+    if (keep)
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true>), dim3(n_tracks), dim3(1024), 0, s, stereo_pairs,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts, pq, pcount,
+                           keep);
+    else
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false>), dim3(n_tracks), dim3(1024), 0, s, stereo_pairs,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts, pq, pcount,
+                           keep);
 }
 
 void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,

@@ -91,6 +91,21 @@ void launch_match_finalize(uint32_t* match_key, const yv_keypoint* keypoints,
                            int thr, yv_match* matches, int32_t* match_count, yv_match* filtered,
                            int32_t* filt_count, int2* match_dj, int32_t* match_lim, hipStream_t s,
                            int32_t* kp_count_copy = nullptr, int n_slots = 0);  // + kp_count[0, n_slots) -> copy
+// The 2-NN match filter (yv_batch_set_match_filter; the values of YV_MATCH_RATIO / YV_MATCH_MUTUAL).
+constexpr int kMatchRatio = 1, kMatchMutual = 2;
+// launch_match that also keeps every query's second-best key (same format, 0xFFFFFFFF: no second train point) in
+// match_key2: exact, first index on ties.
+void launch_match_top2(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
+                       int max_train, uint32_t* match_key, uint32_t* match_key2, hipStream_t s);
+// launch_match_finalize with the filter: consumes (and resets) match_key, match_key2 and rev_key (the matcher's keys
+// of the swapped pairs; untouched 0xFFFFFFFF entries read as "no query"); a query is kept iff distance < limit and
+// the tests in `flags` pass.  Writes nn2[pair][i] = {d1, j1, d2, j2}, rev[pair][j] and keep[pair][i] as well.
+void launch_match_finalize_robust(uint32_t* match_key, uint32_t* match_key2, uint32_t* rev_key,
+                                  const yv_keypoint* keypoints, const int32_t* kp_count, const int32_t* pairs,
+                                  int n_pairs, int max_kp, int thr, int flags, int ratio_num, int ratio_den,
+                                  yv_match* matches, int32_t* match_count, yv_match* filtered, int32_t* filt_count,
+                                  int2* match_dj, int32_t* match_lim, int4* nn2, int32_t* rev, uint8_t* keep,
+                                  hipStream_t s, int32_t* kp_count_copy = nullptr, int n_slots = 0);
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
@@ -134,11 +149,12 @@ void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const
 void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
                         const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
                         const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s);
+                        int32_t* edge_count, hipStream_t s, const uint8_t* keep = nullptr);
+// keep (optional, [pair][max_kp], the match filter's): a match counts only if its query's byte is set
 void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
                           const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
                           const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s);
+                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep = nullptr);
 void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,
                      const int32_t* pcount, int max_kp, double* edge_X, double* edge_uv, int32_t* edge_query,
                      int32_t* edge_count, hipStream_t s);

@@ -1216,11 +1216,38 @@ __device__ __forceinline__ int desc_popcount(const Desc& d) {
     return c;
 }
 
+// Running top-2 of distinct keys: (m1, m2) = the two largest of {m1, m2, x, y}, m1 >= m2 on entry and exit.  The
+// larger of m1 and max(x, y) is the new m1; the second is the largest of what is left: min(m1, max(x, y)), m2 and
+// min(x, y).  5 VALU per two keys.
+__device__ __forceinline__ void top2_push2_i32(int& m1, int& m2, int x, int y) {
+    const int hi = max(x, y), lo = min(x, y);
+    m2 = max(min(m1, hi), max(m2, lo));
+    m1 = max(m1, hi);
+}
+
+// Merge of two running pairs over disjoint key sets: the second largest of the union is the smaller head or one of
+// the tails.  (A max butterfly on m2 alone would lose the smaller head.)
+__device__ __forceinline__ void top2_merge_i32(int& m1, int& m2, int o1, int o2) {
+    m2 = max(min(m1, o1), max(m2, o2));
+    m1 = max(m1, o1);
+}
+
+// the int8 matcher's key -> (distance << 16) | train index
+__device__ __forceinline__ uint32_t mm_decode_key(int v) {
+    const int dot = v >> 16;
+    const uint32_t d = (uint32_t)((256 - dot) >> 1);
+    const uint32_t jj = 0xFFFFu - ((uint32_t)v & 0xFFFFu);
+    return (d << 16) | jj;
+}
+
 // Train lists above 2048 (up to kMaxKp; lists <= 2048 take the FP4 kernel below): the +-1 encoding, dot = 256 -
-// 2 Hamming, key = (dot << 16) + 0xFFFF - j formed per element.
-__global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ desc, const int32_t* __restrict__ kp_count,
-                                                    const int32_t* __restrict__ pairs, int max_kp,
-                                                    uint32_t* __restrict__ match_key) {
+// 2 Hamming, key = (dot << 16) + 0xFFFF - j formed per element.  TOP2: the keys of one query are distinct (j is in
+// the low bits), so the two largest are exactly the nearest and the second nearest train point, ties by index; the
+// second goes to match_key2 in the same format (0xFFFFFFFF: no second train point).
+template <bool TOP2>
+__device__ __forceinline__ void match_body(const Desc* __restrict__ desc, const int32_t* __restrict__ kp_count,
+                                           const int32_t* __restrict__ pairs, int max_kp,
+                                           uint32_t* __restrict__ match_key, uint32_t* __restrict__ match_key2) {
     __shared__ uint4 s_t[2][MM_TC * MM_ROW];
     const int pair = blockIdx.y;
     const int qi = pairs[2 * pair], ti = pairs[2 * pair + 1];
@@ -1252,6 +1279,13 @@ __global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ des
     for (int qt = 0; qt < MM_QT; ++qt)
 #pragma unroll
         for (int r = 0; r < 4; ++r) best[qt][r] = INT_MIN;
+    int best2[TOP2 ? MM_QT : 1][4];
+    if constexpr (TOP2) {
+#pragma unroll
+        for (int qt = 0; qt < MM_QT; ++qt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) best2[qt][r] = INT_MIN;
+    }
 
     // staging: thread -> (train tt = idx >> 4, 16-bit field u = idx & 15), kF fields per thread per chunk
     constexpr int kF = MM_TC * 16 / 256;  // 16-bit fields per thread per chunk
@@ -1313,6 +1347,14 @@ __global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ des
                     }
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
+                        if constexpr (TOP2) {
+                            top2_push2_i32(best[qt][r], best2[qt][r], (int)(((uint32_t)a0[r] << 16) + (uint32_t)bias_a),
+                                           (int)(((uint32_t)b0[r] << 16) + (uint32_t)bias_b));
+                            top2_push2_i32(best[qt + 1][r], best2[qt + 1][r],
+                                           (int)(((uint32_t)a1[r] << 16) + (uint32_t)bias_a),
+                                           (int)(((uint32_t)b1[r] << 16) + (uint32_t)bias_b));
+                            continue;
+                        }
                         best[qt][r] = max(best[qt][r], max((int)(((uint32_t)a0[r] << 16) + (uint32_t)bias_a),
                                                            (int)(((uint32_t)b0[r] << 16) + (uint32_t)bias_b)));
                         best[qt + 1][r] = max(best[qt + 1][r],
@@ -1333,11 +1375,25 @@ __global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ des
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             int v = best[qt][r];
+            const int q = q0 + 16 * MM_QT * wave + 16 * qt + 4 * g + r;
+            if constexpr (TOP2) {
+                // the lanes of a butterfly level hold the pairs of disjoint train columns: a pair merge per level
+                int v2 = best2[qt][r];
+                top2_merge_i32(v, v2, xl::xor_row_i32<8>(v), xl::xor_row_i32<8>(v2));
+                top2_merge_i32(v, v2, xl::xor_row_i32<4>(v), xl::xor_row_i32<4>(v2));
+                top2_merge_i32(v, v2, xl::xor_row_i32<2>(v), xl::xor_row_i32<2>(v2));
+                top2_merge_i32(v, v2, xl::xor_row_i32<1>(v), xl::xor_row_i32<1>(v2));
+                if (col == r && q < nq) {
+                    // a real key is >= -2^24; a column past the list (-2^30 + ...) and the initial INT_MIN are not
+                    match_key[(int64_t)pair * max_kp + q] = v > -(1 << 29) ? mm_decode_key(v) : 0xFFFFFFFFu;
+                    match_key2[(int64_t)pair * max_kp + q] = v2 > -(1 << 29) ? mm_decode_key(v2) : 0xFFFFFFFFu;
+                }
+                continue;
+            }
             v = max(v, xl::xor_row_i32<8>(v));  // DPP butterflies inside the 16-lane group (yavo_xlane.h)
             v = max(v, xl::xor_row_i32<4>(v));
             v = max(v, xl::xor_row_i32<2>(v));
             v = max(v, xl::xor_row_i32<1>(v));
-            const int q = q0 + 16 * MM_QT * wave + 16 * qt + 4 * g + r;
             if (col == r && q < nq) {
                 uint32_t key = 0xFFFFFFFFu;  // empty train set (nt >= 1 always leaves a real key in the row max)
                 if (v != INT_MIN) {
@@ -1350,6 +1406,20 @@ __global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ des
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ desc, const int32_t* __restrict__ kp_count,
+                                                    const int32_t* __restrict__ pairs, int max_kp,
+                                                    uint32_t* __restrict__ match_key) {
+    match_body<false>(desc, kp_count, pairs, max_kp, match_key, nullptr);
+}
+
+__global__ __launch_bounds__(256) void match_top2_kernel(const Desc* __restrict__ desc,
+                                                         const int32_t* __restrict__ kp_count,
+                                                         const int32_t* __restrict__ pairs, int max_kp,
+                                                         uint32_t* __restrict__ match_key,
+                                                         uint32_t* __restrict__ match_key2) {
+    match_body<true>(desc, kp_count, pairs, max_kp, match_key, match_key2);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1377,6 +1447,7 @@ __global__ __launch_bounds__(256) void match_kernel(const Desc* __restrict__ des
 // is a fixed permutation of the bits (the same for A and B), so the products pair matching bits.
 constexpr int MF_TC = 128;               // train descriptors per LDS chunk
 constexpr int MF_ROW = 9;                // uint4 per expanded train row (8 + 1 pad)
+constexpr int MF2_QT = 4, MF2_WPE = 3;   // the top-2 instantiation's query tiles per wave and waves per SIMD
 
 // 32 descriptor bits -> 32 FP4 nibbles (1.0 / 0) in four dwords: bit 4i + k lands in bit 1 of nibble i of dword k,
 // one mask per dword (and a shift for three of them): 7 VALU per descriptor dword, where spreading each byte
@@ -1406,10 +1477,54 @@ __device__ __forceinline__ uint32_t max16_u32(uint32_t best, const mf_v16f& a) {
     return max(best, max(m5, m6));
 }
 
-template <int QT, int WPE>
+// ---- top-2 (the 2-NN mode) ----
+// The keys' of one query are distinct (the train index is in the low bits), so the two largest keys' are exactly
+// (d1, j1) and (d2, j2): the nearest train point and the nearest of the others, ties by the smaller index.  A row past
+// the list and the initial value are 0, below every real key'.  All keys' are non-negative finite floats, whose order
+// is that of their bit patterns: heads and tails are compared as u32, and the one median needed is v_med3_f32 on the
+// same bits (no NaN, no denormal: it returns one of its operands unchanged).
+__device__ __forceinline__ uint32_t umed3_pos(uint32_t a, uint32_t b, uint32_t c) {
+    return __float_as_uint(__builtin_amdgcn_fmed3f(__uint_as_float(a), __uint_as_float(b), __uint_as_float(c)));
+}
+
+// Three sorted pairs (head >= tail) over disjoint keys -> the top-2 of their union, 4 VALU: the largest is the
+// largest head; the second is the median head or the winner's tail, and the other two tails are below their own
+// heads, hence below the median head, so the maximum of all three tails may stand for the winner's.
+__device__ __forceinline__ void top2_merge3(uint32_t h0, uint32_t l0, uint32_t h1, uint32_t l1, uint32_t h2,
+                                            uint32_t l2, uint32_t& m1, uint32_t& m2) {
+    m1 = max(h0, max(h1, h2));
+    m2 = max(umed3_pos(h0, h1, h2), max(l0, max(l1, l2)));
+}
+
+// The running pair and the 16 keys' of one accumulator: five triples give five sorted pairs (max3 + med3 each); with
+// the sixteenth key (tail 0) and the running pair that is seven pairs, merged three at a time.  22 VALU per
+// accumulator (the chain m2 = med3(m1, m2, x), m1 = max(m1, x) takes 32; the 1-NN maximum 8).
+__device__ __forceinline__ void top2_16_u32(uint32_t& m1, uint32_t& m2, const mf_v16f& a) {
+    auto u = [&](int i) { return __float_as_uint(a[i]); };
+    uint32_t h[5], l[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        h[k] = max(u(3 * k), max(u(3 * k + 1), u(3 * k + 2)));
+        l[k] = umed3_pos(u(3 * k), u(3 * k + 1), u(3 * k + 2));
+    }
+    uint32_t a1, a2, b1, b2;
+    top2_merge3(h[0], l[0], h[1], l[1], h[2], l[2], a1, a2);
+    top2_merge3(h[3], l[3], h[4], l[4], u(15), 0u, b1, b2);
+    top2_merge3(a1, a2, b1, b2, m1, m2, m1, m2);
+}
+
+// key' -> (distance << 16) | train index, pa = the query's popcount
+__device__ __forceinline__ uint32_t fp4_decode_key(uint32_t bits, int pa) {
+    const int iv = (int)__uint_as_float(bits) - (1 << 21);
+    const uint32_t d = (uint32_t)(pa - (iv >> 11));
+    const uint32_t jj = 2047u - ((uint32_t)iv & 2047u);
+    return (d << 16) | jj;
+}
+
+template <int QT, int WPE, bool TOP2>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) void match_fp4_kernel(
     const Desc* __restrict__ desc, const int32_t* __restrict__ kp_count, const int32_t* __restrict__ pairs, int max_kp,
-    uint32_t* __restrict__ match_key) {
+    uint32_t* __restrict__ match_key, uint32_t* __restrict__ match_key2) {
     constexpr int QB = 4 * QT * 32;  // queries per workgroup
     __shared__ uint4 s_t[2][MF_TC * MF_ROW];
     __shared__ float s_c[2][MF_TC];  // c_j = (2047 - j) - 2048 popcount(b_j) + 2^21, 0 past the list
@@ -1444,6 +1559,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
     uint32_t best[QT];
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) best[qt] = 0u;
+    uint32_t best2[TOP2 ? QT : 1];
+    if constexpr (TOP2) {
+#pragma unroll
+        for (int qt = 0; qt < QT; ++qt) best2[qt] = 0u;
+    }
 
     // staging: thread -> (train tt = idx >> 3, descriptor dword u = idx & 7), kF dwords per thread per chunk; train
     // tt's chain start c_j from the popcounts of its 8 dwords, summed over their 8 consecutive lanes by DPP (waves 0-1
@@ -1508,8 +1628,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                     a0 = mfma_fp4_32(A[s], B[qt][s], a0);
                     a1 = mfma_fp4_32(A[s], B[qt + 1][s], a1);
                 }
-                best[qt] = max16_u32(best[qt], a0);
-                best[qt + 1] = max16_u32(best[qt + 1], a1);
+                if constexpr (TOP2) {
+                    top2_16_u32(best[qt], best2[qt], a0);
+                    top2_16_u32(best[qt + 1], best2[qt + 1], a1);
+                } else {
+                    best[qt] = max16_u32(best[qt], a0);
+                    best[qt + 1] = max16_u32(best[qt + 1], a1);
+                }
             }
         }
         if (more) {
@@ -1520,7 +1645,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 #pragma unroll
     for (int qt = 0; qt < QT; ++qt) {
         uint32_t v = best[qt];
-        v = max(v, (uint32_t)__shfl_xor((int)v, 32, 64));  // the other lane half's 16 rows of each train block
+        uint32_t v2 = 0u;
+        if constexpr (TOP2) {
+            // the other lane half's pair covers the other 16 rows of each train block: the second of the union is the
+            // smaller head or one of the tails
+            const uint32_t o1 = (uint32_t)__shfl_xor((int)v, 32, 64), o2 = (uint32_t)__shfl_xor((int)best2[qt], 32, 64);
+            v2 = max(min(v, o1), max(best2[qt], o2));
+            v = max(v, o1);
+        } else {
+            v = max(v, (uint32_t)__shfl_xor((int)v, 32, 64));  // the other lane half's 16 rows of each train block
+        }
         // the query's popcount: its expanded fragments hold one set bit per descriptor bit, half in each lane half
         int pa = 0;
 #pragma unroll
@@ -1538,17 +1672,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
                 key = (d << 16) | jj;
             }
             match_key[(int64_t)pair * max_kp + q] = key;
+            // 0 = no second train point (nt < 2): every real key' is >= 2^21 - 2^19
+            if constexpr (TOP2) match_key2[(int64_t)pair * max_kp + q] = v2 != 0u ? fp4_decode_key(v2, pa) : 0xFFFFFFFFu;
         }
     }
 }
 
 namespace {
-template <int QT, int WPE>
+template <int QT, int WPE, bool TOP2>
 void launch_fp4(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                uint32_t* match_key, hipStream_t s) {
+                uint32_t* match_key, uint32_t* match_key2, hipStream_t s) {
     constexpr int QB = 4 * QT * 32;
     dim3 grid((max_kp + QB - 1) / QB, n_pairs);
-    hipLaunchKernelGGL((match_fp4_kernel<QT, WPE>), grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp, match_key);
+    hipLaunchKernelGGL((match_fp4_kernel<QT, WPE, TOP2>), grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp,
+                       match_key, match_key2);
 }
 }  // namespace
 
@@ -1561,7 +1698,18 @@ void launch_match(const Desc* desc, const int32_t* kp_count, const int32_t* pair
     }
     // FP4: 4 query tiles of 32 per wave, 3 waves per SIMD (168 VGPRs; 2 tiles at 4 waves per SIMD: 1.60 ms vs 1.43,
     // profiles/r06/c14)
-    launch_fp4<4, 3>(desc, kp_count, pairs, n_pairs, max_kp, match_key, s);
+    launch_fp4<4, 3, false>(desc, kp_count, pairs, n_pairs, max_kp, match_key, nullptr, s);
+}
+
+void launch_match_top2(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
+                       int max_train, uint32_t* match_key, uint32_t* match_key2, hipStream_t s) {
+    if (max_train > 2048) {
+        dim3 grid((max_kp + MM_QB - 1) / MM_QB, n_pairs);
+        hipLaunchKernelGGL(match_top2_kernel, grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp, match_key,
+                           match_key2);
+        return;
+    }
+    launch_fp4<MF2_QT, MF2_WPE, true>(desc, kp_count, pairs, n_pairs, max_kp, match_key, match_key2, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1587,12 +1735,27 @@ __device__ __forceinline__ int outlier_limit(int min_d, int thr) {
     return twice > thr ? twice : thr;
 }
 
+// ROBUST (the 2-NN match filter): also consumes the second-best keys and the reverse direction's keys (rev_key[pair][j]
+// = train point j's best query, from the matcher run on the swapped pair), and keeps a query iff
+//   d1 < lim  &&  (no YV_MATCH_RATIO || d1 * den < d2 * num in int64)  &&  (no YV_MATCH_MUTUAL || i1(j1) == i).
+// matches / match_dj / match_lim are written as without it; filtered / filt_count hold the kept records only; nn2 =
+// {d1, j1, d2, j2}, rev = i1(j) (-1: not computed or no query), keep = one byte per query.
+struct FinalizeRobust {
+    uint32_t* match_key2;
+    uint32_t* rev_key;
+    int flags, num, den;
+    int4* nn2;
+    int32_t* rev;
+    uint8_t* keep;
+};
+
+template <bool ROBUST>
 __global__ __launch_bounds__(FZ_NT) void match_finalize_kernel(
     uint32_t* __restrict__ match_key, const yv_keypoint* __restrict__ keypoints,
     const int32_t* __restrict__ kp_count, const int32_t* __restrict__ pairs, int max_kp, int thr,
     yv_match* __restrict__ matches, int32_t* __restrict__ match_count, yv_match* __restrict__ filtered,
     int32_t* __restrict__ filt_count, int2* __restrict__ match_dj, int32_t* __restrict__ match_lim,
-    int32_t* __restrict__ kp_count_copy, int n_slots) {
+    int32_t* __restrict__ kp_count_copy, int n_slots, FinalizeRobust rb) {
     __shared__ int s_dist[kMaxKp];
     // the edge build's copy of the run's keypoint counts (the last writer of kp_count, top-K, ran before this kernel)
     if (kp_count_copy && blockIdx.x == 0)
@@ -1613,15 +1776,47 @@ __global__ __launch_bounds__(FZ_NT) void match_finalize_kernel(
         s_dist[i] = d;
         s_j[i] = (k == 0xFFFFFFFFu) ? -1 : (int)(k & 0xFFFFu);
         local_min = min(local_min, d);
+        if constexpr (ROBUST) {
+            uint32_t* keys2 = rb.match_key2 + (int64_t)pair * max_kp;
+            const uint32_t k2 = keys2[i];
+            keys2[i] = 0xFFFFFFFFu;
+            const int j1 = s_j[i];
+            const int d2 = (k2 == 0xFFFFFFFFu) ? 0x7fffffff : (int)(k2 >> 16);
+            const int j2 = (k2 == 0xFFFFFFFFu) ? -1 : (int)(k2 & 0xFFFFu);
+            rb.nn2[(int64_t)pair * max_kp + i] = make_int4(d, j1, d2, j2);
+            bool ok = true;
+            if (rb.flags & kMatchRatio) ok = (int64_t)d * rb.den < (int64_t)d2 * rb.num;
+            if (rb.flags & kMatchMutual) {
+                // the reverse keys are reset only after the barrier of the block minimum below
+                const uint32_t rk = j1 >= 0 ? rb.rev_key[(int64_t)pair * max_kp + j1] : 0xFFFFFFFFu;
+                ok = ok && rk != 0xFFFFFFFFu && (int)(rk & 0xFFFFu) == i;
+            }
+            s_pos[i] = ok ? 1 : 0;
+        }
     }
     const int min_d = block_min_int(local_min, s_tmp);
     const int lim = outlier_limit(min_d, thr);
+    if constexpr (ROBUST) {
+        const int nt = kp_count[ti];
+        uint32_t* rkeys = rb.rev_key + (int64_t)pair * max_kp;
+        for (int j = tid; j < nt; j += FZ_NT) {
+            const uint32_t rk = rkeys[j];
+            rkeys[j] = 0xFFFFFFFFu;
+            rb.rev[(int64_t)pair * max_kp + j] = (rk == 0xFFFFFFFFu) ? -1 : (int)(rk & 0xFFFFu);
+        }
+    }
     int flags[4], cnt = 0;
     int2* dj = match_dj + (int64_t)pair * max_kp;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int i = tid * 4 + u;
         flags[u] = (i < nq && s_dist[i] < lim) ? 1 : 0;
+        if constexpr (ROBUST) {
+            if (i < nq) {
+                flags[u] &= s_pos[i];  // ratio / mutual, written before the block minimum's barrier
+                rb.keep[(int64_t)pair * max_kp + i] = (uint8_t)flags[u];
+            }
+        }
         cnt += flags[u];
         if (i < nq) dj[i] = make_int2(s_dist[i], s_j[i]);
     }
@@ -1686,9 +1881,21 @@ void launch_match_finalize(uint32_t* match_key, const yv_keypoint* keypoints, co
                            const int32_t* pairs, int n_pairs, int max_kp, int thr, yv_match* matches,
                            int32_t* match_count, yv_match* filtered, int32_t* filt_count, int2* match_dj,
                            int32_t* match_lim, hipStream_t s, int32_t* kp_count_copy, int n_slots) {
-    hipLaunchKernelGGL(match_finalize_kernel, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, keypoints, kp_count,
+    hipLaunchKernelGGL(match_finalize_kernel<false>, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, keypoints, kp_count,
                        pairs, max_kp, thr, matches, match_count, filtered, filt_count, match_dj, match_lim,
-                       kp_count_copy, n_slots);
+                       kp_count_copy, n_slots, FinalizeRobust{});
+}
+
+void launch_match_finalize_robust(uint32_t* match_key, uint32_t* match_key2, uint32_t* rev_key,
+                                  const yv_keypoint* keypoints, const int32_t* kp_count, const int32_t* pairs,
+                                  int n_pairs, int max_kp, int thr, int flags, int ratio_num, int ratio_den,
+                                  yv_match* matches, int32_t* match_count, yv_match* filtered, int32_t* filt_count,
+                                  int2* match_dj, int32_t* match_lim, int4* nn2, int32_t* rev, uint8_t* keep,
+                                  hipStream_t s, int32_t* kp_count_copy, int n_slots) {
+    const FinalizeRobust rb{match_key2, rev_key, flags, ratio_num, ratio_den, nn2, rev, keep};
+    hipLaunchKernelGGL(match_finalize_kernel<true>, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, keypoints, kp_count,
+                       pairs, max_kp, thr, matches, match_count, filtered, filt_count, match_dj, match_lim,
+                       kp_count_copy, n_slots, rb);
 }
 
 // removeOutliers over a caller-supplied Matches list (n <= kMaxKp), one workgroup.
