@@ -172,6 +172,12 @@ void or_em_det_poly(const double* B, double* c);
 int or_solve_poly(const double* c, int n0, int max_iters, double* roots);
 /* EMEstimatorCallback::runKernel on 5 normalised correspondences; models [10][9]; returns the model count */
 int or_em_kernel(const double* q1, const double* q2, double* models);
+/* The same two with a trace of the data-dependent arms taken (tests assert on it that their corpus reaches them).
+ * or_solve_poly_ex trace: {trimmed degree, sweeps run (fewer than max_iters: no root moved), factors skipped because
+ * two iterates coincided}.  or_em_kernel_ex trace: {first singular LU pivot index + 1 (0: regular), trimmed degree,
+ * sweeps, coincident-factor skips, roots rejected as complex, roots rejected by solveZ}. */
+int or_solve_poly_ex(const double* c, int n0, int max_iters, double* roots, int trace[3]);
+int or_em_kernel_ex(const double* q1, const double* q2, double* models, int trace[6]);
 /* (p - c) / f as OpenCV's MatExpr evaluates it */
 void or_normalize_points(const double* pts, int n, double fx, double fy, double cx, double cy, double* out);
 /* findEssentialMat(pts1, pts2, focal, (ppx, ppy), RANSAC, prob, threshold, mask) with maxIters; pts [n][2] pixels.

@@ -158,7 +158,7 @@ void or_em_coeff_mat(const double* EE, double* A) {
 
 /* cv::invert(DECOMP_LU) of an n x n (n > 3): LUImpl<double> on a copy with b = I, eps = 100 DBL_EPSILON; on a
  * singular pivot the result is all zeros.  A is read with row stride lda. */
-static int lu_inverse(const double* A, int lda, int n, double* inv) {
+static int lu_inverse(const double* A, int lda, int n, double* inv, int* singular_at) {
     double a[100], b[100];
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j) {
@@ -173,6 +173,7 @@ static int lu_inverse(const double* A, int lda, int n, double* inv) {
             if (fabs(a[j * n + i]) > fabs(a[k * n + i])) k = j;
         if (fabs(a[k * n + i]) < eps) {
             ok = 0;
+            if (singular_at) *singular_at = i + 1;
             break;
         }
         if (k != i) {
@@ -246,8 +247,11 @@ static cplx cdiv(cplx a, cplx b) {
     cplx r = {(a.re * b.re + a.im * b.im) * t, (-a.re * b.im + a.im * b.re) * t};
     return r;
 }
-int or_solve_poly(const double* c, int n0, int max_iters, double* roots_out) {
+/* trace (may be NULL): 0 the trimmed degree, 1 the sweeps run (the last, update-free one included), 2 the factors
+ * skipped because two iterates coincided exactly */
+int or_solve_poly_ex(const double* c, int n0, int max_iters, double* roots_out, int trace[3]) {
     cplx coeffs[16], roots[16];
+    int skips = 0;
     for (int i = 0; i <= n0; ++i) { coeffs[i].re = c[i]; coeffs[i].im = 0.0; }
     int n = n0;
     for (; n > 1; n--) {
@@ -268,6 +272,7 @@ int or_solve_poly(const double* c, int n0, int max_iters, double* roots_out) {
             for (int j = 0; j < n; j++) {
                 num = cadd(cmul(num, p), coeffs[n - j - 1]);
                 if (j != i && (p.re != roots[j].re || p.im != roots[j].im)) denom = cmul(denom, csub(p, roots[j]));
+                else if (j != i) skips++;
             }
             num = cdiv(num, denom);
             roots[i] = csub(p, num);
@@ -282,11 +287,21 @@ int or_solve_poly(const double* c, int n0, int max_iters, double* roots_out) {
         roots_out[2 * i] = roots[i].re;
         roots_out[2 * i + 1] = roots[i].im;
     }
+    if (trace) {
+        trace[0] = n;
+        trace[1] = iter < max_iters ? iter + 1 : max_iters;
+        trace[2] = skips;
+    }
     return iter;
 }
+int or_solve_poly(const double* c, int n0, int max_iters, double* roots_out) {
+    return or_solve_poly_ex(c, n0, max_iters, roots_out, NULL);
+}
 
-/* EMEstimatorCallback::runKernel on 5 normalised correspondences q1[5][2], q2[5][2] -> up to 10 models [10][9] */
-int or_em_kernel(const double* q1, const double* q2, double* models) {
+/* EMEstimatorCallback::runKernel on 5 normalised correspondences q1[5][2], q2[5][2] -> up to 10 models [10][9].
+ * trace (may be NULL): 0 the first singular LU pivot index + 1 (0: not singular), 1 solvePoly's trimmed degree, 2 its
+ * sweeps, 3 its coincident-factor skips, 4 the roots rejected as complex, 5 the roots rejected by solveZ */
+int or_em_kernel_ex(const double* q1, const double* q2, double* models, int trace[6]) {
     /* SVD::compute(Q 5 x 9, FULL_UV): m < n -> temp_a = Q (5 rows of 9), JacobiSVD(m = 9, n = 5, n1 = 9); vt = At */
     double At[81], Vt5[25], W[5];
     memset(At, 0, sizeof At);
@@ -302,7 +317,8 @@ int or_em_kernel(const double* q1, const double* q2, double* models) {
     double A[200];
     or_em_coeff_mat(EE, A);
     double inv[100], M[100];
-    lu_inverse(A, 20, 10, inv);
+    int singular_at = 0, ptrace[3], n_complex = 0, n_solvez = 0;
+    lu_inverse(A, 20, 10, inv, &singular_at);
     for (int i = 0; i < 10; ++i)
         for (int j = 0; j < 10; ++j) {
             double s = 0;
@@ -323,10 +339,13 @@ int or_em_kernel(const double* q1, const double* q2, double* models) {
     }
     double c[11], roots[20];
     or_em_det_poly(B, c);
-    or_solve_poly(c, 10, 300, roots);
+    or_solve_poly_ex(c, 10, 300, roots, ptrace);
     int count = 0;
     for (int i = 0; i < 10; i++) {
-        if (fabs(roots[2 * i + 1]) > 1e-10) continue;
+        if (fabs(roots[2 * i + 1]) > 1e-10) {
+            n_complex++;
+            continue;
+        }
         const double z1 = roots[2 * i], z2 = z1 * z1, z3 = z2 * z1, z4 = z3 * z1;
         double bz[9];
         for (int j = 0; j < 3; j++) {
@@ -338,7 +357,10 @@ int or_em_kernel(const double* q1, const double* q2, double* models) {
         double w3[3], vt3[9];
         or_cv_svd(bz, 3, w3, NULL, vt3); /* SVD::solveZ: last row of vt */
         const double* xy1 = vt3 + 6;
-        if (fabs(xy1[2]) < 1e-10) continue;
+        if (fabs(xy1[2]) < 1e-10) {
+            n_solvez++;
+            continue;
+        }
         const double xs = xy1[0] / xy1[2], ys = xy1[1] / xy1[2], zs = z1;
         double ev[9];
         for (int k = 0; k < 9; ++k) ev[k] = ((EE[0 * 9 + k] * xs + EE[1 * 9 + k] * ys) + EE[2 * 9 + k] * zs) + EE[3 * 9 + k];
@@ -351,8 +373,17 @@ int or_em_kernel(const double* q1, const double* q2, double* models) {
         for (k = 0; k < 9; ++k) models[count * 9 + k] = ev[k] * sc;
         count++;
     }
+    if (trace) {
+        trace[0] = singular_at;
+        trace[1] = ptrace[0];
+        trace[2] = ptrace[1];
+        trace[3] = ptrace[2];
+        trace[4] = n_complex;
+        trace[5] = n_solvez;
+    }
     return count;
 }
+int or_em_kernel(const double* q1, const double* q2, double* models) { return or_em_kernel_ex(q1, q2, models, NULL); }
 
 /* EMEstimatorCallback::computeError + findInliers; returns the inlier count */
 static int em_inliers(const double* m1, const double* m2, int n, const double* E, float t, uint8_t* mask) {

@@ -76,6 +76,8 @@ class Oracle:
             "or_em_det_poly": (None, [_P, _P]),
             "or_solve_poly": (_I, [_P, _I, _I, _P]),
             "or_em_kernel": (_I, [_P, _P, _P]),
+            "or_solve_poly_ex": (_I, [_P, _I, _I, _P, _P]),
+            "or_em_kernel_ex": (_I, [_P, _P, _P, _P]),
             "or_normalize_points": (None, [_P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, _P]),
             "or_find_essential": (_I, [_P, _P, _I, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                        ctypes.c_double, _I, _P, _P, _P]),
@@ -390,6 +392,24 @@ class Oracle:
         roots = np.zeros((len(c) - 1, 2), np.float64)
         it = self.lib.or_solve_poly(_p(c), len(c) - 1, max_iters, _p(roots))
         return roots[:, 0] + 1j * roots[:, 1], it
+
+    def em_kernel_ex(self, q1, q2):
+        """-> (models [10, 9] (zeros past the count), count, trace dict: singular (first singular LU pivot index + 1, or
+        0), degree, sweeps, skips, complex, solvez)."""
+        q1 = np.ascontiguousarray(q1, np.float64).reshape(5, 2)
+        q2 = np.ascontiguousarray(q2, np.float64).reshape(5, 2)
+        models = np.zeros((10, 9), np.float64)
+        tr = np.zeros(6, np.int32)
+        n = self.lib.or_em_kernel_ex(_p(q1), _p(q2), _p(models), _p(tr))
+        return models, n, dict(zip(("singular", "degree", "sweeps", "skips", "complex", "solvez"), map(int, tr)))
+
+    def solve_poly_ex(self, c, max_iters=300):
+        """-> (roots [n0, 2] (re, im; zeros past the trimmed degree), trace dict: degree, sweeps, skips)."""
+        c = np.ascontiguousarray(c, np.float64)
+        roots = np.zeros((len(c) - 1, 2), np.float64)
+        tr = np.zeros(3, np.int32)
+        self.lib.or_solve_poly_ex(_p(c), len(c) - 1, max_iters, _p(roots), _p(tr))
+        return roots, dict(zip(("degree", "sweeps", "skips"), map(int, tr)))
 
     def find_essential(self, pts1, pts2, focal=718.856, pp=(607.1928, 185.2157), prob=0.999, threshold=1.0,
                        max_iters=1000):

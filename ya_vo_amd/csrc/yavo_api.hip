@@ -2156,6 +2156,22 @@ int yv_recover_pose_batch(yv_essential* es, const double* d_E, const float* d_pt
     return check_launch();
 }
 
+// Test entry point (tests/test_gpu_essential_degenerate.py; like yv_debug_xlane not part of the public headers): the
+// five-point solver alone, in the workspace's own form, on n_sets given subsets of five normalised correspondences
+// d_q1 / d_q2 [n_sets][5][2] -> d_models [n_sets][10][9] (zeros past a subset's count) and d_nmod [n_sets].  Overwrites
+// list 0 of the workspace.
+int yv_debug_ess_models(yv_essential* es, const double* d_q1, const double* d_q2, int n_sets, double* d_models,
+                        int32_t* d_nmod, void* stream) {
+    if (!es || !d_q1 || !d_q2 || !d_models || !d_nmod || n_sets <= 0 ||
+        n_sets > std::min(es->P.chunk, es->P.max_iters) || 5 * (int64_t)n_sets > es->P.max_points)
+        return YV_ERR_INVALID;
+    if (set_device(es->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : es->ctx->stream;
+    const int rc = yavo::launch_debug_ess_models(es->P, d_q1, d_q2, n_sets, d_models, d_nmod, s);
+    if (rc != 0) return rc == -1 ? YV_ERR_INVALID : YV_ERR_HIP;
+    return check_launch();
+}
+
 // the context's cached one-list essential workspace with room for `points` points and `iters` RANSAC iterations
 static int ctx_essential(yv_ctx* ctx, int points, int iters, yv_essential** out) {
     yv_essential* es = ctx->ess_cache;

@@ -1252,7 +1252,116 @@ __global__ void rp_select_kernel(int n_pairs, EssParams P, double* __restrict__ 
     if (good_out) good_out[pair] = g[pick];
 }
 
+// ------------------------------------------------------------------------------------------------
+// test entry points (tests/test_gpu_essential_degenerate.py; like yv_debug_xlane not part of the public headers)
+// ------------------------------------------------------------------------------------------------
+// solvePoly alone, as em_models runs it: the same trim loop and the same switch over dk_group<N> / dk_solve<N>, in
+// ess_models_kernel<kGroup>'s lane layout (polynomial k on row k % 4 of workgroup k / 4, or on lane k % 64 of
+// workgroup k / 64).  roots [n][10][2]: (re, im) after the 1e-100 flush, zeros past the trimmed degree.
+template <bool kGroup>
+__global__ __launch_bounds__(64) void debug_solve_poly_kernel(const double* __restrict__ coeffs, int n,
+                                                              double* __restrict__ roots) {
+    const int lane = threadIdx.x;
+    const int g = kGroup ? lane / kModelRow : lane;
+    const int r = kGroup ? lane - g * kModelRow : 0;
+    const int base = kGroup ? g * kModelRow : lane;
+    const int k = blockIdx.x * (kGroup ? kModelIters : 64) + g;
+    if ((kGroup && r >= kModelGroup) || k >= n) return;  // whole groups leave together
+    const uint64_t gmask = kGroup ? ((1ull << kModelGroup) - 1ull) << base : 1ull << lane;
+    double c[11];
+#pragma unroll
+    for (int i = 0; i < 11; ++i) c[i] = coeffs[(int64_t)k * 11 + i];
+    int nn = 10;
+    for (; nn > 1; nn--)
+        if (fabs(c[nn]) + fabs(0.0) > DBL_EPSILON) break;
+    double* out = roots + (int64_t)k * 20;
+    if constexpr (kGroup) {
+        double rre = 0, rim = 0;
+        switch (nn) {  // group-uniform
+            case 10: dk_group<10>(c, r, base, gmask, rre, rim); break;
+            case 9: dk_group<9>(c, r, base, gmask, rre, rim); break;
+            case 8: dk_group<8>(c, r, base, gmask, rre, rim); break;
+            case 7: dk_group<7>(c, r, base, gmask, rre, rim); break;
+            case 6: dk_group<6>(c, r, base, gmask, rre, rim); break;
+            case 5: dk_group<5>(c, r, base, gmask, rre, rim); break;
+            case 4: dk_group<4>(c, r, base, gmask, rre, rim); break;
+            case 3: dk_group<3>(c, r, base, gmask, rre, rim); break;
+            case 2: dk_group<2>(c, r, base, gmask, rre, rim); break;
+            default: dk_group<1>(c, r, base, gmask, rre, rim); break;
+        }
+        out[2 * r] = rre;
+        out[2 * r + 1] = rim;
+    } else {
+        double rre[10], rim[10];
+        switch (nn) {
+            case 10: dk_solve<10>(c, rre, rim); break;
+            case 9: dk_solve<9>(c, rre, rim); break;
+            case 8: dk_solve<8>(c, rre, rim); break;
+            case 7: dk_solve<7>(c, rre, rim); break;
+            case 6: dk_solve<6>(c, rre, rim); break;
+            case 5: dk_solve<5>(c, rre, rim); break;
+            case 4: dk_solve<4>(c, rre, rim); break;
+            case 3: dk_solve<3>(c, rre, rim); break;
+            case 2: dk_solve<2>(c, rre, rim); break;
+            default: dk_solve<1>(c, rre, rim); break;
+        }
+#pragma unroll
+        for (int i = 0; i < 10; ++i) {
+            out[2 * i] = rre[i];
+            out[2 * i + 1] = rim[i];
+        }
+    }
+}
+
+// list 0 of the workspace as n_sets five-point subsets in order: the identity draws and the list's state
+__global__ void debug_models_setup_kernel(EssParams P, int n_sets) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 5 * n_sets) P.idx[i] = i;
+    if (i == 0) {
+        int32_t* st = P.state;
+        st[0] = n_sets;
+        st[1] = st[2] = st[3] = st[4] = 0;
+        st[5] = 5 * n_sets;
+    }
+}
+
 }  // namespace ess
+
+extern "C" int yv_debug_ess_solve_poly(int group_form, const double* d_coeffs /* [n][11] */, int n,
+                                       double* d_roots /* [n][10][2] */, void* stream) {
+    if (!d_coeffs || !d_roots || n < 0) return -1;
+    if (n == 0) return 0;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (group_form)
+        hipLaunchKernelGGL(ess::debug_solve_poly_kernel<true>, dim3((n + ess::kModelIters - 1) / ess::kModelIters),
+                           dim3(64), 0, s, d_coeffs, n, d_roots);
+    else
+        hipLaunchKernelGGL(ess::debug_solve_poly_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, s, d_coeffs, n,
+                           d_roots);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// ess_models_kernel, launched as launch_find_essential launches it, on n_sets given five-point subsets (already
+// normalised): they become list 0 of the workspace with the identity as its draws
+int launch_debug_ess_models(const EssParams& P, const double* q1, const double* q2, int n_sets, double* models,
+                            int32_t* nmod, hipStream_t s) {
+    if (n_sets <= 0 || n_sets > P.chunk || n_sets > P.max_iters || 5 * n_sets > P.max_points) return -1;
+    const size_t pts = sizeof(double) * 10 * (size_t)n_sets;
+    if (hipMemcpyAsync(P.m1, q1, pts, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(P.m2, q2, pts, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemsetAsync(P.models, 0, sizeof(double) * 90 * (size_t)n_sets, s) != hipSuccess)
+        return -2;
+    hipLaunchKernelGGL(ess::debug_models_setup_kernel, dim3((5 * n_sets + 255) / 256), dim3(256), 0, s, P, n_sets);
+    if (P.chunk == kEssChunkWide)
+        hipLaunchKernelGGL(ess::ess_models_kernel<true>, dim3((P.chunk + ess::kModelIters - 1) / ess::kModelIters, 1),
+                           dim3(64), 0, s, P, 0);
+    else
+        hipLaunchKernelGGL(ess::ess_models_kernel<false>, dim3((P.chunk + 63) / 64, 1), dim3(64), 0, s, P, 0);
+    if (hipMemcpyAsync(models, P.models, sizeof(double) * 90 * (size_t)n_sets, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipMemcpyAsync(nmod, P.nmod, sizeof(int32_t) * (size_t)n_sets, hipMemcpyDeviceToDevice, s) != hipSuccess)
+        return -2;
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
 
 #ifdef YAVO_LM_PROFILE
 extern "C" int yv_debug_ess_prof(unsigned long long* out) {

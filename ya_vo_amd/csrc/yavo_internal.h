@@ -194,6 +194,10 @@ struct EssRun {
 void launch_find_essential(const EssParams& P, const EssRun& r, const float* pts1, const float* pts2,
                            const int32_t* counts, int n_pairs, int pts_stride, double* E, uint8_t* mask,
                            int32_t* found, int32_t* stats, hipStream_t s);
+// test entry point behind yv_debug_ess_models (yavo_api.hip): the model kernel of the workspace's form on n_sets given
+// five-point subsets q1 / q2 [n_sets][5][2]; models [n_sets][10][9] (zeros past a subset's count), nmod [n_sets]
+int launch_debug_ess_models(const EssParams& P, const double* q1, const double* q2, int n_sets, double* models,
+                            int32_t* nmod, hipStream_t s);
 struct Mat3 {
     double v[9];
 };
