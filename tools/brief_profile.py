@@ -1,4 +1,8 @@
-"""Phase breakdown of brief_kernel (lane 0 of each workgroup, shader-clock cycles) from the profiling build.
+"""Phase breakdown of brief_kernel (lane 0 of each worker, shader-clock cycles) from the profiling build: per band
+the staging, the descriptors and the hand-over (the wave's last descriptor store to the band's closing barrier passed,
+which is where a worker waits for its slowest wave and for the next item); per worker the bands taken and its life; and
+the workers resident per CU over the launch.  A build of the one-band-per-workgroup revision (no band counts in its
+slots) is read as workers of one band each.
 
     make -C ya_vo_amd/csrc prof && python tools/brief_profile.py [--frames 512]"""
 import argparse
@@ -39,11 +43,18 @@ def main():
     ctx.sync()
     ms, _ = b.stage_times()
     assert lib.yv_debug_brief_prof(buf.ctypes.data) == 0
-    wgs = min(((H + 31) // 32) * 2 * B, 16384)
-    per = buf[:wgs, :2].astype(np.float64).mean(0)
-    print(f"brief {ms[2]:.4f} ms for {2 * B} images, {wgs} workgroups; mean cycles per workgroup (lane 0): "
-          f"{per.sum():.0f}")
-    for name, v in zip(("list scan + band staging", "descriptors + records"), per):
+    items = ((H + 31) // 32) * 2 * B
+    wgs = int(np.count_nonzero(buf[:, 3]))  # the slots this process's launches wrote
+    bands = (buf[:wgs, 4] >> np.uint64(32)).astype(np.float64)
+    legacy = not bands.any()
+    if legacy:
+        bands[:] = 1
+    cyc = np.stack([buf[:wgs, 0], buf[:wgs, 1], buf[:wgs, 5] >> np.uint64(32)], 1).astype(np.float64)
+    per = cyc.sum(0) / max(bands.sum(), 1)
+    print(f"brief {ms[2]:.4f} ms for {2 * B} images, {items} bands, {wgs} workers"
+          f"{' (one band per workgroup)' if legacy else ''}; bands per worker mean {bands.mean():.1f} "
+          f"min {bands.min():.0f} max {bands.max():.0f}; mean cycles per band (lane 0): {per.sum():.0f}")
+    for name, v in zip(("list + band staging", "descriptors + records", "hand-over (barrier, next item)"), per):
         print(f"  {name:30s} {v:9.0f}  ({100 * v / max(per.sum(), 1):5.1f}%)")
     # residency: workgroups per CU over time (s_memrealtime, 100 MHz; CU = (XCC, SE, SH, CU) of HW_ID)
     t0 = buf[:wgs, 2].astype(np.int64)
@@ -62,9 +73,10 @@ def main():
             mx = max(mx, cur)
         busy[int(c)] = (int(m.sum()), mx, float((t1[m] - t0[m]).sum()) / span)
     v = np.array(list(busy.values()), np.float64)
-    print(f"  span {span / 100:.1f} us over {len(busy)} CUs; workgroups per CU mean {v[:, 0].mean():.1f}; max resident "
+    print(f"  span {span / 100:.1f} us over {len(busy)} CUs; workers per CU mean {v[:, 0].mean():.1f}; max resident "
           f"per CU: mean {v[:, 1].mean():.2f} max {v[:, 1].max():.0f}; mean resident over the span {v[:, 2].mean():.2f}; "
-          f"mean workgroup life {(t1 - t0).mean() / 100:.2f} us")
+          f"mean worker life {(t1 - t0).mean() / 100:.2f} us (min {(t1 - t0).min() / 100:.2f}, "
+          f"max {(t1 - t0).max() / 100:.2f})")
     b.close()
     ctx.close()
 

@@ -59,6 +59,8 @@ struct yv_ctx {
     };
     std::vector<PendingD2H> pending;
     hipStream_t side = nullptr;  // yv_side_stream: a stream on a hardware queue of its own, made on first use
+    int cus = 0;                 // the device's CU count (0: not asked yet), see brief_workers
+    int brief_cap = 0;           // yv_debug_set_brief_workers: a cap on brief_kernel's workers (0: none)
 };
 
 namespace yavo {
@@ -87,6 +89,7 @@ struct yv_batch {
     int32_t* kp_band = nullptr;     // [slot][max_kp] int4 {row, col, id, slot}: the kept keypoints by BRIEF band
     int32_t* band_off = nullptr;    // [slot][kMaxBands + 1]
     int32_t* brief_loff = nullptr;  // [256][2] BRIEF test offsets in the band's LDS layout (launch_brief)
+    int32_t* brief_heads = nullptr; // [8] brief_kernel's band queue heads: zeroed by top-K / kp_boundary_kernel
     int loff_version = -1;          // the ctx offsets_version brief_loff was formed from (-1: never)
     bool counts_copied = false;     // this run's finalize wrote kp_count_build (the asynchronous build's copy)
     yv_keypoint* keypoints = nullptr;
@@ -239,7 +242,7 @@ int dalloc(T** p, size_t count) {
 void batch_free(yv_batch* b) {
     if (!b) return;
     void* ptrs[] = {b->cand_keys, b->cand_count, b->cand_seen, b->det_rc,   b->det_resp,    b->det_count, b->kp_src, b->kp_band, b->band_off,
-                    b->brief_loff, b->kp_count,  b->kp_count_build, b->keypoints,  b->desc, b->blur,   b->pairs,     b->match_key,
+                    b->brief_loff, b->brief_heads, b->kp_count,  b->kp_count_build, b->keypoints,  b->desc, b->blur,   b->pairs,     b->match_key,
                     b->matches,   b->match_count, b->filtered, b->filt_count, b->staging,  b->match_dj,
                     b->match_lim, b->tracks,     b->track_K,  b->T_right,    b->edge_X,    b->edge_uv,
                     b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers,
@@ -504,6 +507,26 @@ void yv_destroy(yv_ctx* ctx) {
 
 void* yv_stream(yv_ctx* ctx) { return ctx ? reinterpret_cast<void*>(ctx->stream) : nullptr; }
 
+// the device's CU count (256 when the runtime does not tell)
+static int ctx_cus(yv_ctx* ctx) {
+    if (ctx->cus <= 0) {
+        int cus = 0;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0) {
+            (void)hipGetLastError();
+            cus = 256;
+        }
+        ctx->cus = cus;
+    }
+    return ctx->cus;
+}
+
+// brief_kernel's worker limit: two LDS regions of <= 80 KiB per CU (one where a wider band's region is larger),
+// under the test cap of yv_debug_set_brief_workers
+static int brief_workers(yv_ctx* ctx, int W) {
+    const int w = ctx_cus(ctx) * yavo::brief_workers_per_cu(W);
+    return ctx->brief_cap > 0 ? std::min(w, ctx->brief_cap) : w;
+}
+
 // HIP binds each new stream to one of a few hardware queues (GPU_MAX_HW_QUEUES, 4 by default), reusing the least
 // used one once they are all taken, so two streams can end up on one queue and run in order: work meant to overlap
 // then serialises (the sequence's BA stream against the context stream measured 0.067 vs 0.097 s for 1000 frames, one
@@ -513,9 +536,7 @@ void* yv_side_stream(yv_ctx* ctx) {
     if (!ctx) return nullptr;
     if (ctx->side) return reinterpret_cast<void*>(ctx->side);
     if (set_device(ctx) != YV_OK) return nullptr;
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || cus <= 0)
-        cus = 256;
+    const int cus = ctx_cus(ctx);
     std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
     for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
     if (hipExtStreamCreateWithCUMask(&ctx->side, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
@@ -653,6 +674,7 @@ int yv_batch_create(yv_ctx* ctx, int max_images, int H, int W, int max_kp, int m
     rc |= dalloc(&b->kp_band, ns * nk * 4);
     rc |= dalloc(&b->band_off, ns * (size_t)(yavo::kMaxBands + 1));
     rc |= dalloc(&b->brief_loff, 512);
+    rc |= dalloc(&b->brief_heads, (size_t)yavo::kBriefHeads);
     rc |= dalloc(&b->keypoints, ns * nk);
     rc |= dalloc(&b->desc, ns * nk);
     rc |= dalloc(&b->blur, (size_t)max_images * (size_t)yavo::blur_image_bytes(H, W));
@@ -814,7 +836,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     rc |= record_stage(b, s, run, 1);
     if (b->overlap_mode == 2) rc |= launch_deferred_after(b, s);
     yavo::launch_topk(b->cand_keys, b->cap, b->cand_count, b->cand_seen, n_images, H, W, K, keep, b->det_rc,
-                      b->det_resp, b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, s);
+                      b->det_resp, b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
     rc |= record_stage(b, s, run, 2);
     if (b->overlap_mode == 4) rc |= launch_deferred_after(b, s);  // after top-K
     // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
@@ -825,7 +847,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     const bool new_loff = b->loff_version != ctx->offsets_version;
     b->loff_version = ctx->offsets_version;
     yavo::launch_brief(b->blur, n_images, H, W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, K, b->keypoints,
-                       b->desc, b->brief_loff, new_loff, s);
+                       b->desc, b->brief_loff, new_loff, b->brief_heads, brief_workers(ctx, W), s);
     rc |= record_stage(b, s, run, 3);
     if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
     b->run_flags = b->n_pairs > 0 ? b->match_flags : 0;
@@ -1284,7 +1306,7 @@ int yv_detect(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, int max
     yavo::launch_fast_harris(b->staging, 1, H, W, W, (int64_t)H * W, ctx->fast_thr, ctx->harris_eigen, b->cand_keys, b->cap,
                              b->cand_count, s);
     yavo::launch_topk(b->cand_keys, b->cap, b->cand_count, b->cand_seen, 1, H, W, b->max_kp, keep, b->det_rc, b->det_resp,
-                      b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, s);
+                      b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->det_count, sizeof(int32_t), s));
     YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->cand_seen, sizeof(uint32_t), s));
@@ -1316,11 +1338,11 @@ int yv_describe(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const
     YV_HIP(stage_h2d(ctx, b->det_count, ctx->h_pinned, sizeof(int32_t), s));
     yavo::launch_blur9(b->staging, 1, H, W, W, (int64_t)H * W, ctx->k9, b->blur, s);
     yavo::launch_kp_boundary(b->det_rc, b->det_count, 1, H, W, b->max_kp, b->kp_src, b->kp_count, b->kp_band,
-                             b->band_off, s);
+                             b->band_off, b->brief_heads, s);
     const bool new_loff = b->loff_version != ctx->offsets_version;
     b->loff_version = ctx->offsets_version;
     yavo::launch_brief(b->blur, 1, H, W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, b->max_kp, b->keypoints,
-                       b->desc, b->brief_loff, new_loff, s);
+                       b->desc, b->brief_loff, new_loff, b->brief_heads, brief_workers(ctx, W), s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     YV_HIP(stage_d2h(ctx, ctx->h_pinned + 2, b->kp_count, sizeof(int32_t), s));
     YV_HIP(stage_sync(ctx, s));
@@ -2154,6 +2176,15 @@ int yv_recover_pose_batch(yv_essential* es, const double* d_E, const float* d_pt
     for (int i = 0; i < 9; ++i) k.v[i] = K[i];
     yavo::launch_recover_pose(es->P, d_E, d_pts1, d_pts2, d_counts, n_pairs, pts_stride, k, d_R, d_t, d_good, s);
     return check_launch();
+}
+
+// Test entry point (tests/test_gpu_brief_persistent.py; like yv_debug_xlane not part of the public headers): caps the
+// number of brief_kernel's workers for the context's later launches, so that few workers walk many bands; 0 restores
+// the default (two per CU).
+int yv_debug_set_brief_workers(yv_ctx* ctx, int n) {
+    if (!ctx || n < 0) return YV_ERR_INVALID;
+    ctx->brief_cap = n;
+    return YV_OK;
 }
 
 // Test entry point (tests/test_gpu_essential_degenerate.py; like yv_debug_xlane not part of the public headers): the

@@ -35,6 +35,14 @@ constexpr int kFastTileH = 56;
 __host__ __device__ constexpr int blur_pitch(int W) { return (W + 1 + 127) & ~127; }
 // BRIEF's LDS band row stride: >= W + 1 (column W holds the next row's first pixel, see brief_kernel), 16-B rows
 __host__ __device__ constexpr int brief_lds_stride(int W) { return (W + 1 + 15) & ~15; }
+// brief_kernel's LDS region: the band (49 rows), the band's keypoint list, the next band's index / lo / count
+__host__ __device__ constexpr size_t brief_lds_bytes(int W) {
+    return (size_t)(kBandRows + 17) * brief_lds_stride(W) + sizeof(uint32_t) * kMaxKp + 16;
+}
+// brief_kernel is a grid of persistent workers that take (band, image) items from a queue with kBriefHeads heads, one
+// per XCD label (blockIdx % 8): as many workers per CU as LDS regions fit the CU's 160 KiB (2 up to W = 1327)
+constexpr int kBriefHeads = 8;
+inline int brief_workers_per_cu(int W) { return brief_lds_bytes(W) <= 80 * 1024 ? 2 : 1; }
 // Blurred images are laid out [image][H][blur_pitch(W)].
 __host__ __device__ constexpr int64_t blur_image_bytes(int H, int W) { return (int64_t)H * blur_pitch(W); }
 // XCD-aware block order (MI355X: 8 XCDs, each with its own L2; blocks are observed to round-robin over them by
@@ -65,18 +73,23 @@ void launch_blur9(const uint8_t* imgs, int n_images, int H, int W, int stride, i
                   const uint16_t* k9_host, uint8_t* blur, hipStream_t s);
 // Per-image top-K (response desc, index asc) + checkBoundry compaction.
 // cand_count is copied to cand_seen and reset to 0 after it is read (ready for the next detection).
+// brief_heads: the kBriefHeads queue heads of the launch_brief that follows on s, zeroed here (no launch of their own).
 void launch_topk(const uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, uint32_t* cand_seen, int n_images,
                  int H, int W, int max_kp, int keep, int32_t* det_rc, float* det_resp, int32_t* det_count,
-                 int32_t* kp_src, int32_t* kp_count, int32_t* kp_band, int32_t* band_off, hipStream_t s);
+                 int32_t* kp_src, int32_t* kp_count, int32_t* kp_band, int32_t* band_off, int32_t* brief_heads,
+                 hipStream_t s);
 // checkBoundry compaction of externally supplied points (det_rc / det_count already on the device).
 void launch_kp_boundary(const int32_t* det_rc, const int32_t* det_count, int n_images, int H, int W,
                         int max_kp, int32_t* kp_src, int32_t* kp_count, int32_t* kp_band, int32_t* band_off,
-                        hipStream_t s);
+                        int32_t* brief_heads, hipStream_t s);
 // BRIEF: writes KeyPoint records + packed descriptors.  loff: a 2 KB device scratch of the caller holding the tests'
 // LDS offsets for this W, formed on stream s first when new_loff (the offsets table or W changed since it was formed).
+// heads: the band queue's kBriefHeads heads, zero on entry (launch_topk / launch_kp_boundary on s); the grid is
+// min(max_workers, bands x images) workers.
 void launch_brief(const uint8_t* blur, int n_images, int H, int W, const int8_t* offsets,
                   const int32_t* kp_src, const int32_t* kp_band, const int32_t* band_off, int max_kp,
-                  yv_keypoint* keypoints, Desc* desc, int32_t* loff, bool new_loff, hipStream_t s);
+                  yv_keypoint* keypoints, Desc* desc, int32_t* loff, bool new_loff, int32_t* heads, int max_workers,
+                  hipStream_t s);
 // Pack KeyPoint records -> descriptors (host-supplied keypoints).
 void launch_pack_desc(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp,
                       Desc* desc, hipStream_t s);
