@@ -124,6 +124,18 @@ int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* 
 int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags,
                     int ratio_num, int ratio_den, yv_match* out, int* n_out, uint8_t* keep);
 
+/* ---- gated matching: only train points inside a window around the query (beyond the reference; exact) ---- */
+/* A gate is {drow_lo, drow_hi, dcol_lo, dcol_hi} (yv_keypoint: x = row, y = column).  Train point j is a candidate
+ * of query i iff drow_lo <= t[j].x - q[i].x <= drow_hi and dcol_lo <= t[j].y - q[i].y <= dcol_hi, and (d1, j1),
+ * (d2, j2) and i1(j) above are taken over the candidates only (i1(j) over the queries j is a candidate of): no
+ * candidate gives d1 = INT32_MAX, j1 = -1, fewer than two d2 = INT32_MAX, j2 = -1, no such query i1 = -1.  A rectified
+ * stereo pair (left = query) is {-r, r, -max_disparity, 0}, a temporal pair a window {-h, h, -w, w}.
+ * yv_match_knn2 under a gate: out capacity nq, rev (may be NULL) capacity nt.  YV_ERR_INVALID for a NULL gate, q, t
+ * or out, a negative count, a gate with lo > hi or a bound outside [-65535, 65535], or a keypoint with x or y outside
+ * [0, 65535]; YV_ERR_CAPACITY for nq or nt above 4096; all checked before the context, as in yv_match_knn2. */
+int yv_match_gated(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, const int32_t gate[4],
+                   yv_match2* out, int32_t* rev);
+
 /* ---- batched device pipeline (inputs resident in HBM) ---------------------------------------------- */
 /* A batch owns device workspace for up to max_images images of H x W and max_pairs match pairs.  Slot
  * index max_images is the "carry" slot: it holds the keypoints / descriptors of one image of the
@@ -157,6 +169,14 @@ typedef struct yv_batch_match2_view {
 /* Device views of the filter's arrays (the last run with a filter on); YV_ERR_INVALID before the filter was ever
  * switched on. */
 int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v);
+/* The gates of the following runs, one per pair of yv_batch_set_pairs (gates[4 * p ..] as in yv_match_gated); gates
+ * == NULL or n_pairs == 0 switches gating off (the default).  With gates set, yv_batch_run replaces its matcher
+ * launches (forward, top-2 and swapped pairs alike) by the gated matcher; removeOutliers, the match filter, the
+ * tracks and every view array work as before, on the gated (d1, j1), (d2, j2) and i1: a query without a candidate
+ * has distance INT32_MAX, train index -1 and is never kept.  yv_batch_set_pairs clears the gates.  The device
+ * buffers are allocated by the first call that sets gates.  YV_ERR_INVALID for a NULL batch, n_pairs different from
+ * the batch's pair count, or a gate yv_match_gated would reject. */
+int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates /* [4 * n_pairs] */, int n_pairs);
 /* Tracking (PnP) over the last run's matches: track t = {stereo_pair, temporal_pair} (pair indices of
  * yv_batch_set_pairs) where the stereo pair's query image (frame k left) is the temporal pair's train
  * image.  Each frame-(k-1) keypoint kept by removeOutliers in the temporal pair whose frame-k keypoint is

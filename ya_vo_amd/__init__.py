@@ -95,6 +95,8 @@ SIGNATURES = {
     "yv_match_robust": (_I, [_P, _P, _I, _P, _I, _I, _I, _I, _I, _P, ctypes.POINTER(_I), _P]),
     "yv_batch_set_match_filter": (_I, [_P, _I, _I, _I]),
     "yv_batch_match2_view_get": (_I, [_P, ctypes.POINTER(_BatchMatch2View)]),
+    "yv_match_gated": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
+    "yv_batch_set_match_gates": (_I, [_P, _P, _I]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -503,6 +505,23 @@ class Context(_GeomMixin):
                "yv_match_knn2")
         return nn2[:len(q)].copy(), rev[:len(t)].copy()
 
+    def match_gated(self, q: np.ndarray, t: np.ndarray, gate) -> Tuple[np.ndarray, np.ndarray]:
+        """yv_match_gated: match_knn2 over the train points inside gate = (drow_lo, drow_hi, dcol_lo, dcol_hi) on train
+        minus query position (x = row, y = column) -> (nn2 [nq] MATCH2_DTYPE, rev [nt] int32)."""
+        q = np.ascontiguousarray(q, dtype=KEYPOINT_DTYPE)
+        t = np.ascontiguousarray(t, dtype=KEYPOINT_DTYPE)
+        g = np.ascontiguousarray(np.asarray(gate, dtype=np.int32).reshape(4))
+        nq, nt = len(q), len(t)
+        if nq == 0:  # an empty array has no address to pass
+            q = np.zeros(1, KEYPOINT_DTYPE)
+        if nt == 0:
+            t = np.zeros(1, KEYPOINT_DTYPE)
+        nn2 = np.zeros(max(nq, 1), MATCH2_DTYPE)
+        rev = np.zeros(max(nt, 1), np.int32)
+        _check(self.lib.yv_match_gated(self.handle, _ptr(q), nq, _ptr(t), nt, _ptr(g), _ptr(nn2), _ptr(rev)),
+               "yv_match_gated")
+        return nn2[:nq].copy(), rev[:nt].copy()
+
     def match_robust(self, q: np.ndarray, t: np.ndarray, thr: int = 20, ratio=(4, 5),
                      mutual: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """yv_match_robust: matchFeatures + removeOutliers(thr) + Lowe's ratio test d1 * den < d2 * num (ratio =
@@ -624,6 +643,15 @@ class Batch:
         ratio test on, mutual the cross-check; both off (the default) is the reference's behaviour."""
         flags, num, den = _match_filter_args(ratio, mutual)
         _check(self.lib.yv_batch_set_match_filter(self.handle, flags, num, den), "yv_batch_set_match_filter")
+
+    def set_match_gates(self, gates=None) -> None:
+        """The gates of the following runs (yv_batch_set_match_gates): one (drow_lo, drow_hi, dcol_lo, dcol_hi) per
+        pair of set_pairs, on train minus query position; None (the default) switches gating off."""
+        if gates is None:
+            _check(self.lib.yv_batch_set_match_gates(self.handle, None, 0), "yv_batch_set_match_gates")
+            return
+        g = np.ascontiguousarray(np.asarray(gates, dtype=np.int32).reshape(-1, 4))
+        _check(self.lib.yv_batch_set_match_gates(self.handle, _ptr(g), len(g)), "yv_batch_set_match_gates")
 
     def match2_view(self) -> _BatchMatch2View:
         """Device arrays of the match filter (yv_batch_match2_view_get): nn2 [max_pairs][max_kp] MATCH2_DTYPE, rev

@@ -113,6 +113,13 @@ struct yv_batch {
     int4* nn2 = nullptr;            // [max_pairs][max_kp] {d1, j1, d2, j2}
     int32_t* rev = nullptr;         // [max_pairs][max_kp]
     uint8_t* keep = nullptr;        // [max_pairs][max_kp]
+    // the match gates (yv_batch_set_match_gates): allocated by the first call that sets gates
+    bool gated = false, gate_alloc = false;
+    int gate_bands = 0;             // bands of kGateBandRows rows in gate_band's tables
+    int gate_cols = 0, gate_shift = 0;  // column cells per band, of (1 << gate_shift) columns
+    int32_t* gates = nullptr;       // [max_pairs][4] {drow_lo, drow_hi, dcol_lo, dcol_hi}
+    uint2* gate_sorted = nullptr;   // [slot][max_kp] {row | column << 16, keypoint index} by (band, column cell)
+    int32_t* gate_band = nullptr;   // [slot][gate_bands + 1] band starts
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)
@@ -246,7 +253,8 @@ void batch_free(yv_batch* b) {
                     b->matches,   b->match_count, b->filtered, b->filt_count, b->staging,  b->match_dj,
                     b->match_lim, b->tracks,     b->track_K,  b->T_right,    b->edge_X,    b->edge_uv,
                     b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers,
-                    b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep};
+                    b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep,
+                    b->gates, b->gate_sorted, b->gate_band};
     if (b->bstream) (void)hipStreamSynchronize(b->bstream);
     if (b->side) (void)hipStreamSynchronize(b->side);
     for (void* p : ptrs)
@@ -428,6 +436,47 @@ int ensure_match2(yv_batch* b) {
     YV_HIP(hipStreamSynchronize(s));
     b->m2_alloc = true;
     return upload_pairs_rev(b);
+}
+
+// {drow_lo, drow_hi, dcol_lo, dcol_hi}: lo <= hi, every bound inside [-65535, 65535]
+bool gate_ok(const int32_t* g) {
+    for (int k = 0; k < 4; ++k)
+        if (g[k] < -yavo::kGateMaxCoord || g[k] > yavo::kGateMaxCoord) return false;
+    return g[0] <= g[1] && g[2] <= g[3];
+}
+
+// the gated matcher's device buffers, on first use (pairs_rev is the match filter's: the reverse launch needs both).
+// The buckets cover max_row + 1 rows and max_col + 1 columns: the widest column cells that keep n_bands * col_cells
+// inside kGateMaxCells, 64 columns at the least.
+int ensure_gates(yv_batch* b, int max_row, int max_col) {
+    if (b->gate_alloc) return YV_OK;
+    const int n_bands = max_row / yavo::kGateBandRows + 1;
+    int shift = 6;
+    while (n_bands * ((max_col >> shift) + 1) > yavo::kGateMaxCells && shift < 16) ++shift;
+    if (n_bands * ((max_col >> shift) + 1) > yavo::kGateMaxCells) return YV_ERR_CAPACITY;
+    const size_t nk = (size_t)b->max_kp, np = (size_t)std::max(b->max_pairs, 1), ns = (size_t)b->nslots;
+    int rc = YV_OK;
+    rc |= dalloc(&b->gates, np * 4);
+    rc |= dalloc(&b->gate_sorted, ns * nk);
+    rc |= dalloc(&b->gate_band, ns * (size_t)(n_bands + 1));
+    if (rc != YV_OK) return YV_ERR_HIP;  // batch_free releases what was allocated
+    b->gate_bands = n_bands;
+    b->gate_cols = (max_col >> shift) + 1;
+    b->gate_shift = shift;
+    b->gate_alloc = true;
+    return YV_OK;
+}
+
+// The gated replacements of launch_match / launch_match_top2 (+ the swapped pairs): the order of every slot, then the
+// matcher over the first n_pairs pairs.  top2 / with_rev need the match filter's buffers.
+void launch_gated_matches(yv_batch* b, int n_pairs, bool top2, bool with_rev, hipStream_t s) {
+    yavo::launch_gate_sort(b->keypoints, b->kp_count, b->nslots, b->max_kp, b->gate_bands, b->gate_cols, b->gate_shift,
+                           b->gate_sorted, b->gate_band, s);
+    yavo::launch_match_gated(b->desc, b->kp_count, b->pairs, n_pairs, b->max_kp, b->gate_bands, b->gate_sorted,
+                             b->gate_band, b->gates, false, b->match_key, top2 ? b->match_key2 : nullptr, s);
+    if (with_rev)
+        yavo::launch_match_gated(b->desc, b->kp_count, b->pairs_rev, n_pairs, b->max_kp, b->gate_bands, b->gate_sorted,
+                                 b->gate_band, b->gates, true, b->rev_key, nullptr, s);
 }
 
 int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
@@ -732,7 +781,29 @@ int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs, int n_pairs) {
     b->h_pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
     b->n_pairs = n_pairs;
     b->n_tracks = 0;  // tracks refer to pair indices: set them again
+    b->gated = false;  // and so do the gates
     return upload_pairs_rev(b);
+}
+
+int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates, int n_pairs) {
+    if (!b) return YV_ERR_INVALID;
+    if (!gates || n_pairs == 0) {
+        b->gated = false;
+        return YV_OK;
+    }
+    if (n_pairs != b->n_pairs) return YV_ERR_INVALID;
+    for (int p = 0; p < n_pairs; ++p)
+        if (!gate_ok(gates + 4 * p)) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    const int rc = ensure_gates(b, b->H - 1, b->W - 1);
+    if (rc != YV_OK) return rc;
+    // a run in flight reads the table
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    YV_HIP(hipMemcpyAsync(b->gates, gates, sizeof(int32_t) * 4 * (size_t)n_pairs, hipMemcpyHostToDevice,
+                          b->ctx->stream));
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    b->gated = true;
+    return YV_OK;
 }
 
 int yv_batch_set_match_filter(yv_batch* b, int flags, int ratio_num, int ratio_den) {
@@ -856,9 +927,13 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     const bool copy_counts = b->n_pairs > 0 && b->overlap && b->build_async && b->lk_step == 0;
     if (b->run_flags != 0) {
         // the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
-        yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, b->match_key2, s);
-        if (b->match_flags & YV_MATCH_MUTUAL)
-            yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, b->n_pairs, K, K, b->rev_key, s);
+        if (b->gated) {
+            launch_gated_matches(b, b->n_pairs, true, (b->match_flags & YV_MATCH_MUTUAL) != 0, s);
+        } else {
+            yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, b->match_key2, s);
+            if (b->match_flags & YV_MATCH_MUTUAL)
+                yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, b->n_pairs, K, K, b->rev_key, s);
+        }
         rc |= record_stage(b, s, run, 4);
         yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs,
                                            b->n_pairs, K, match_thr, b->match_flags, b->ratio_num, b->ratio_den,
@@ -866,7 +941,8 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
                                            b->match_lim, b->nn2, b->rev, b->keep, s,
                                            copy_counts ? b->kp_count_build : nullptr, b->nslots);
     } else if (b->n_pairs > 0) {
-        yavo::launch_match(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, s);
+        if (b->gated) launch_gated_matches(b, b->n_pairs, false, false, s);
+        else yavo::launch_match(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, s);
         rc |= record_stage(b, s, run, 4);
         yavo::launch_match_finalize(b->match_key, b->keypoints, b->kp_count, b->pairs, b->n_pairs, K, match_thr,
                                     b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj,
@@ -1449,6 +1525,51 @@ int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* 
     const int st = match2_single(ctx, q, nq, t, nt, 0, 0, 0, 1, rev != nullptr, s);
     if (st != YV_OK) return st;
     yv_batch* b = ctx->single;
+    YV_HIP(stage_d2h(ctx, out, b->nn2, sizeof(yv_match2) * (size_t)nq, s));
+    if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, b->rev, sizeof(int32_t) * (size_t)nt, s));
+    YV_HIP(stage_sync(ctx, s));
+    return YV_OK;
+}
+
+int yv_match_gated(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, const int32_t gate[4],
+                   yv_match2* out, int32_t* rev) {
+    if (!gate || !q || !t || !out || nq < 0 || nt < 0 || !gate_ok(gate)) return YV_ERR_INVALID;
+    if (nq > yavo::kMaxKp || nt > yavo::kMaxKp) return YV_ERR_CAPACITY;
+    for (int i = 0; i < nq; ++i)
+        if (q[i].x < 0 || q[i].x > yavo::kGateMaxCoord || q[i].y < 0 || q[i].y > yavo::kGateMaxCoord)
+            return YV_ERR_INVALID;
+    for (int j = 0; j < nt; ++j)
+        if (t[j].x < 0 || t[j].x > yavo::kGateMaxCoord || t[j].y < 0 || t[j].y > yavo::kGateMaxCoord)
+            return YV_ERR_INVALID;
+    if (!ctx) return yv_device_count() > 0 ? YV_ERR_INVALID : YV_ERR_NODEVICE;
+    if (nq == 0) {
+        if (rev)
+            for (int j = 0; j < nt; ++j) rev[j] = -1;  // no query
+        return YV_OK;
+    }
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = ctx->stream;
+    int st = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    st = ensure_match2(b);
+    if (st != YV_OK) return st;
+    st = ensure_gates(b, yavo::kGateMaxCoord, yavo::kGateMaxCoord);  // positions come from the caller: all 16 bits
+    if (st != YV_OK) return st;
+    const size_t nk = (size_t)b->max_kp;
+    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
+    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + nk, t, sizeof(yv_keypoint) * (size_t)nt, s));
+    ctx->h_pinned[0] = nq;
+    ctx->h_pinned[1] = nt;
+    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
+    YV_HIP(stage_h2d(ctx, b->gates, gate, 4 * sizeof(int32_t), s));
+    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
+    launch_gated_matches(b, 1, true, rev != nullptr, s);
+    yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs, 1,
+                                       b->max_kp, 0, 0, 0, 1, b->matches, b->match_count, b->filtered, b->filt_count,
+                                       b->match_dj, b->match_lim, b->nn2, b->rev, b->keep, s);
+    if (check_launch() != YV_OK) return YV_ERR_HIP;
     YV_HIP(stage_d2h(ctx, out, b->nn2, sizeof(yv_match2) * (size_t)nq, s));
     if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, b->rev, sizeof(int32_t) * (size_t)nt, s));
     YV_HIP(stage_sync(ctx, s));

@@ -119,6 +119,22 @@ void launch_match_finalize_robust(uint32_t* match_key, uint32_t* match_key2, uin
                                   yv_match* matches, int32_t* match_count, yv_match* filtered, int32_t* filt_count,
                                   int2* match_dj, int32_t* match_lim, int4* nn2, int32_t* rev, uint8_t* keep,
                                   hipStream_t s, int32_t* kp_count_copy = nullptr, int n_slots = 0);
+// The gated matcher (yv_match_gated / yv_batch_set_match_gates, yavo_match_gate.hip).  Per slot, the keypoints
+// bucketed by cell = (band of kGateBandRows rows, column >> col_shift): sorted[slot][max_kp] = {row | column << 16,
+// keypoint index} cell by cell, band_start[slot][n_bands + 1] = first entry of every band.  n_bands * kGateBandRows
+// covers every row, col_cells << col_shift every column, n_bands * col_cells <= kGateMaxCells; rows and columns are
+// 16-bit.
+constexpr int kGateBandRows = 32;
+constexpr int kGateMaxCells = 8192;
+constexpr int kGateMaxCoord = 65535;
+void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp, int n_bands,
+                      int col_cells, int col_shift, uint2* sorted, int32_t* band_start, hipStream_t s);
+// launch_match / launch_match_top2 (match_key2 != nullptr) over the train points inside each pair's gate: gates[pair]
+// = {drow_lo, drow_hi, dcol_lo, dcol_hi} on train minus query position; mirror: the gate of the swapped pair list.
+// Writes a key for every query of every pair, 0xFFFFFFFF where the gate holds no (second) train point.
+void launch_match_gated(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
+                        int n_bands, const uint2* sorted, const int32_t* band_start, const int32_t* gates, bool mirror,
+                        uint32_t* match_key, uint32_t* match_key2, hipStream_t s);
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
