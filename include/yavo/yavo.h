@@ -136,6 +136,33 @@ int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint
 int yv_match_gated(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, const int32_t gate[4],
                    yv_match2* out, int32_t* rev);
 
+/* ---- keypoint selection: non-maximum suppression and per-cell quotas (beyond the reference; exact) ---- */
+/* Every FAST corner has the key (~ord(response)) << 32 | row * W + col the cut ranks by: a smaller key is better
+ * (higher response first, then the smaller row-major index), and the keys of one image are distinct.  Before the cut:
+ *   nms_radius = r in 0..8 (0: off): a corner survives iff no other corner of the image with |drow| <= r and
+ *     |dcol| <= r has a smaller key.  Simultaneous (a suppressed corner still suppresses), among corners only;
+ *   per_cell = q in 0..4096 (0: off; cell_rows, cell_cols in [8, 8192], ignored for q = 0): cells are anchored at pixel
+ *     (0, 0), cell(p) = (row / cell_rows, col / cell_cols); of each cell's survivors the q with the smallest keys stay.
+ * What remains goes through the cut unchanged: the best min(max_corners, max_kp) in key order, then checkBoundry and
+ * BRIEF as before; n_candidates / the view's cand_count keep counting the corners before selection and cut.  The
+ * setting lives on the context: yv_detect, yv_select_corners and every yv_batch_run of the context's batches follow it
+ * from the next call on.  All off (the default) launches exactly the reference's cut.  With q > 0 an H x W image may
+ * have at most 8192 cells, ceil(H / cell_rows) * ceil(W / cell_cols) <= 8192: those three calls return
+ * YV_ERR_CAPACITY otherwise, before any copy or launch (a batch is left exactly as it was).  The extra device
+ * buffers (one more candidate list per image + counters) are allocated by the first run or call with selection on.
+ * YV_ERR_INVALID for r outside 0..8, q outside 0..4096 or, with q > 0, a cell side outside [8, 8192], all checked
+ * before the context; then for a NULL context. */
+int yv_set_keypoint_select(yv_ctx* ctx, int nms_radius, int cell_rows, int cell_cols, int per_cell);
+/* Selection + cut of a host list: n corners rc[2 * i ..] = (row, col) of an H x W image with responses resp[i], under
+ * the context's selection and keep = min(max_corners, max_kp), in key order into out_rc / out_resp (capacity max_kp;
+ * out_resp may be NULL), *n_out = number written.  Positions must be distinct (not checked).  Responses are compared
+ * through the key, so any bit pattern is ordered; -0.0 and 0.0 differ.  Checked before the context: YV_ERR_INVALID
+ * for a NULL rc, resp, out_rc or n_out, n < 0, max_kp < 0, H < 9, W < 9 or a position outside [0, H) x [0, W);
+ * YV_ERR_CAPACITY for n > (H - 8) * (W - 8); then, as in yv_match_knn2, YV_ERR_NODEVICE for a NULL context on a
+ * machine without a GPU. */
+int yv_select_corners(yv_ctx* ctx, int H, int W, const int32_t* rc, const float* resp, int n, int max_kp,
+                      int32_t* out_rc, float* out_resp, int* n_out);
+
 /* ---- batched device pipeline (inputs resident in HBM) ---------------------------------------------- */
 /* A batch owns device workspace for up to max_images images of H x W and max_pairs match pairs.  Slot
  * index max_images is the "carry" slot: it holds the keypoints / descriptors of one image of the

@@ -97,6 +97,8 @@ SIGNATURES = {
     "yv_batch_match2_view_get": (_I, [_P, ctypes.POINTER(_BatchMatch2View)]),
     "yv_match_gated": (_I, [_P, _P, _I, _P, _I, _P, _P, _P]),
     "yv_batch_set_match_gates": (_I, [_P, _P, _I]),
+    "yv_set_keypoint_select": (_I, [_P, _I, _I, _I, _I]),
+    "yv_select_corners": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, ctypes.POINTER(_I)]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -441,6 +443,32 @@ class Context(_GeomMixin):
 
     def set_fast_params(self, intensity_threshold: int = 40, max_corners: int = 2000) -> None:
         _check(self.lib.yv_set_fast_params(self.handle, intensity_threshold, max_corners), "yv_set_fast_params")
+
+    def set_keypoint_select(self, nms_radius: int = 0, cell=None, per_cell: int = 0) -> None:
+        """Keypoint selection before the cut (yv_set_keypoint_select): non-maximum suppression among the corners within
+        nms_radius (0: off) and at most per_cell (0: off) keypoints per cell of cell = (rows, cols) pixels.  detect,
+        select_corners and every run of this context's batches follow it; all off is the reference's cut."""
+        rows, cols = (int(cell[0]), int(cell[1])) if cell is not None else (0, 0)
+        _check(self.lib.yv_set_keypoint_select(self.handle, int(nms_radius), rows, cols, int(per_cell)),
+               "yv_set_keypoint_select")
+
+    def select_corners(self, rc: np.ndarray, resp: np.ndarray, H: int, W: int,
+                       max_kp: int = 2000) -> Tuple[np.ndarray, np.ndarray]:
+        """yv_select_corners: the context's selection and the cut on a list of corners rc [n, 2] (row, col; distinct)
+        with responses resp [n] of an H x W image -> (rc [m, 2] int32, resp [m] float32) in key order."""
+        rc = np.ascontiguousarray(rc, dtype=np.int32).reshape(-1, 2)
+        resp = np.ascontiguousarray(resp, dtype=np.float32).reshape(-1)
+        if len(rc) != len(resp):
+            raise ValueError("rc and resp differ in length")
+        n = len(rc)
+        if n == 0:  # an empty array has no address to pass
+            rc, resp = np.zeros((1, 2), np.int32), np.zeros(1, np.float32)
+        out_rc = np.zeros((max(max_kp, 1), 2), np.int32)
+        out_resp = np.zeros(max(max_kp, 1), np.float32)
+        m = ctypes.c_int()
+        _check(self.lib.yv_select_corners(self.handle, int(H), int(W), _ptr(rc), _ptr(resp), n, int(max_kp),
+                                          _ptr(out_rc), _ptr(out_resp), ctypes.byref(m)), "yv_select_corners")
+        return out_rc[:m.value].copy(), out_resp[:m.value].copy()
 
     def set_harris_eigen(self, flavour: int = 0) -> None:
         """cv::eigen flavour of the Harris response: 0 = OpenCV JacobiImpl_ (default), 1 = HAVE_EIGEN (Eigen 3.4)."""

@@ -61,6 +61,8 @@ struct yv_ctx {
     hipStream_t side = nullptr;  // yv_side_stream: a stream on a hardware queue of its own, made on first use
     int cus = 0;                 // the device's CU count (0: not asked yet), see brief_workers
     int brief_cap = 0;           // yv_debug_set_brief_workers: a cap on brief_kernel's workers (0: none)
+    // keypoint selection before the cut (yv_set_keypoint_select): all off = the reference's cut
+    int sel_radius = 0, sel_rows = 0, sel_cols = 0, sel_q = 0;
 };
 
 namespace yavo {
@@ -120,6 +122,11 @@ struct yv_batch {
     int32_t* gates = nullptr;       // [max_pairs][4] {drow_lo, drow_hi, dcol_lo, dcol_hi}
     uint2* gate_sorted = nullptr;   // [slot][max_kp] {row | column << 16, keypoint index} by (band, column cell)
     int32_t* gate_band = nullptr;   // [slot][gate_bands + 1] band starts
+    // keypoint selection (yv_set_keypoint_select): allocated by the first run or call with selection on
+    bool sel_alloc = false;
+    uint64_t* sel_keys = nullptr;   // [max_images][cap] the bucketed candidate lists
+    int32_t* sel_starts = nullptr;  // [max_images][kSelMaxCells + 1] the buckets' starts
+    uint32_t* sel_counts = nullptr; // [3][max_images] filtered counts after suppression / quota, top-K's unused "seen"
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)
@@ -254,7 +261,7 @@ void batch_free(yv_batch* b) {
                     b->match_lim, b->tracks,     b->track_K,  b->T_right,    b->edge_X,    b->edge_uv,
                     b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers,
                     b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep,
-                    b->gates, b->gate_sorted, b->gate_band};
+                    b->gates, b->gate_sorted, b->gate_band, b->sel_keys, b->sel_starts, b->sel_counts};
     if (b->bstream) (void)hipStreamSynchronize(b->bstream);
     if (b->side) (void)hipStreamSynchronize(b->side);
     for (void* p : ptrs)
@@ -479,6 +486,54 @@ void launch_gated_matches(yv_batch* b, int n_pairs, bool top2, bool with_rev, hi
                                  b->gate_band, b->gates, true, b->rev_key, nullptr, s);
 }
 
+// ---- keypoint selection (yv_set_keypoint_select) ----
+bool select_args_ok(int nms_radius, int cell_rows, int cell_cols, int per_cell) {
+    if (nms_radius < 0 || nms_radius > yavo::kSelMaxRadius || per_cell < 0 || per_cell > yavo::kSelMaxPerCell)
+        return false;
+    if (per_cell > 0 && (cell_rows < yavo::kSelMinCell || cell_rows > yavo::kSelMaxCell ||
+                         cell_cols < yavo::kSelMinCell || cell_cols > yavo::kSelMaxCell))
+        return false;
+    return true;
+}
+
+bool select_on(const yv_ctx* ctx) { return ctx->sel_radius > 0 || ctx->sel_q > 0; }
+
+// the quota's cells of an H x W image fit the bucket kernel's counter table
+bool select_fits(const yv_ctx* ctx, int H, int W) {
+    if (ctx->sel_q <= 0) return true;
+    const int64_t cy = (H + ctx->sel_rows - 1) / ctx->sel_rows, cx = (W + ctx->sel_cols - 1) / ctx->sel_cols;
+    return cy * cx <= yavo::kSelMaxCells;
+}
+
+// the selection's device buffers, on first use
+int ensure_select(yv_batch* b) {
+    if (b->sel_alloc) return YV_OK;
+    const size_t ni = (size_t)b->max_images;
+    int rc = YV_OK;
+    rc |= dalloc(&b->sel_keys, ni * (size_t)b->cap);
+    rc |= dalloc(&b->sel_starts, ni * (size_t)(yavo::kSelMaxCells + 1));
+    rc |= dalloc(&b->sel_counts, 3 * ni);
+    if (rc != YV_OK) return YV_ERR_HIP;  // batch_free releases what was allocated
+    b->sel_alloc = true;
+    return YV_OK;
+}
+
+// launch_topk over the detect kernel's lists, behind the context's selection when one is on (select_fits and
+// ensure_select have passed)
+void launch_select_topk(yv_batch* b, int n_images, int keep, hipStream_t s) {
+    const yv_ctx* ctx = b->ctx;
+    uint32_t* count = b->cand_count;
+    uint32_t* seen = b->cand_seen;
+    if (select_on(ctx)) {
+        count = yavo::launch_select(b->cand_keys, b->cap, b->cand_count, b->cand_seen, n_images, b->H, b->W,
+                                    ctx->sel_radius, ctx->sel_rows, ctx->sel_cols, ctx->sel_q, b->sel_keys,
+                                    b->sel_starts, b->sel_counts, s);
+        seen = b->sel_counts + 2 * (size_t)b->max_images;  // the corners before the filter are in cand_seen already
+    }
+    yavo::launch_topk(b->cand_keys, b->cap, count, seen, n_images, b->H, b->W, b->max_kp, keep, b->det_rc, b->det_resp,
+                      b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
+}
+
 int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
     if (!b->timing || run < 0) return YV_OK;
     if (b->timing == 2 && stage > 1) return YV_OK;  // detect-only: the two events around the detect kernel
@@ -656,6 +711,15 @@ int yv_set_fast_params(yv_ctx* ctx, int intensity_threshold, int max_corners) {
         return YV_ERR_INVALID;
     ctx->fast_thr = intensity_threshold;
     ctx->max_corners = max_corners;
+    return YV_OK;
+}
+
+int yv_set_keypoint_select(yv_ctx* ctx, int nms_radius, int cell_rows, int cell_cols, int per_cell) {
+    if (!select_args_ok(nms_radius, cell_rows, cell_cols, per_cell) || !ctx) return YV_ERR_INVALID;
+    ctx->sel_radius = nms_radius;
+    ctx->sel_q = per_cell;
+    ctx->sel_rows = per_cell > 0 ? cell_rows : 0;
+    ctx->sel_cols = per_cell > 0 ? cell_cols : 0;
     return YV_OK;
 }
 
@@ -888,6 +952,11 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
     const int H = b->H, W = b->W, K = b->max_kp;
     const int keep = std::min(ctx->max_corners, K);
+    if (select_on(ctx)) {  // before any copy or launch: a refused run leaves the batch as it was
+        if (!select_fits(ctx, H, W)) return YV_ERR_CAPACITY;
+        const int st = ensure_select(b);
+        if (st != YV_OK) return st;
+    }
     if (b->pending_carry >= 0 && join_build(b, s) != YV_OK) return YV_ERR_HIP;
     if (b->pending_carry >= 0) {
         const size_t c = (size_t)b->pending_carry, dst = (size_t)b->max_images, nk = (size_t)K;
@@ -906,8 +975,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
                              b->cand_count, ctx->k9, b->blur, s);
     rc |= record_stage(b, s, run, 1);
     if (b->overlap_mode == 2) rc |= launch_deferred_after(b, s);
-    yavo::launch_topk(b->cand_keys, b->cap, b->cand_count, b->cand_seen, n_images, H, W, K, keep, b->det_rc,
-                      b->det_resp, b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
+    launch_select_topk(b, n_images, keep, s);
     rc |= record_stage(b, s, run, 2);
     if (b->overlap_mode == 4) rc |= launch_deferred_after(b, s);  // after top-K
     // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
@@ -1378,11 +1446,15 @@ int yv_detect(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, int max
     yv_batch* b = ctx->single;
     hipStream_t s = ctx->stream;
     const int keep = std::min(std::min(ctx->max_corners, max_kp), b->max_kp);
+    if (select_on(ctx)) {
+        if (!select_fits(ctx, H, W)) return YV_ERR_CAPACITY;
+        st = ensure_select(b);
+        if (st != YV_OK) return st;
+    }
     if (upload_image(b, img, stride, s) != YV_OK) return YV_ERR_HIP;
     yavo::launch_fast_harris(b->staging, 1, H, W, W, (int64_t)H * W, ctx->fast_thr, ctx->harris_eigen, b->cand_keys, b->cap,
                              b->cand_count, s);
-    yavo::launch_topk(b->cand_keys, b->cap, b->cand_count, b->cand_seen, 1, H, W, b->max_kp, keep, b->det_rc, b->det_resp,
-                      b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
+    launch_select_topk(b, 1, keep, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->det_count, sizeof(int32_t), s));
     YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->cand_seen, sizeof(uint32_t), s));
@@ -1395,6 +1467,53 @@ int yv_detect(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, int max
     }
     *n = k;
     if (n_candidates) *n_candidates = ctx->h_pinned[1];
+    return YV_OK;
+}
+
+int yv_select_corners(yv_ctx* ctx, int H, int W, const int32_t* rc, const float* resp, int n, int max_kp,
+                      int32_t* out_rc, float* out_resp, int* n_out) {
+    if (!rc || !resp || !out_rc || !n_out || n < 0 || max_kp < 0 || H < 9 || W < 9) return YV_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (rc[2 * i] < 0 || rc[2 * i] >= H || rc[2 * i + 1] < 0 || rc[2 * i + 1] >= W) return YV_ERR_INVALID;
+    if ((int64_t)n > (int64_t)(H - 8) * (W - 8)) return YV_ERR_CAPACITY;
+    if (!ctx) return yv_device_count() > 0 ? YV_ERR_INVALID : YV_ERR_NODEVICE;
+    if (!select_fits(ctx, H, W)) return YV_ERR_CAPACITY;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    int st = ensure_single(ctx, H, W);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    if (select_on(ctx)) {
+        st = ensure_select(b);
+        if (st != YV_OK) return st;
+    }
+    hipStream_t s = ctx->stream;
+    const int keep = std::min(std::min(ctx->max_corners, max_kp), b->max_kp);
+    // the detect kernel's key, from the response's bits as they are: (~ord) << 32 | row * W + col
+    if (n > 0) {
+        uint64_t* keys = reinterpret_cast<uint64_t*>(stage_alloc(ctx, sizeof(uint64_t) * (size_t)n, s));
+        if (!keys) return YV_ERR_HIP;
+        for (int i = 0; i < n; ++i) {
+            uint32_t u;
+            std::memcpy(&u, resp + i, sizeof(u));
+            const uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            keys[i] = ((uint64_t)(~ord) << 32) | (uint64_t)((uint32_t)rc[2 * i] * (uint32_t)W + (uint32_t)rc[2 * i + 1]);
+        }
+        YV_HIP(hipMemcpyAsync(b->cand_keys, keys, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    ctx->h_pinned[0] = n;
+    YV_HIP(stage_h2d(ctx, b->cand_count, ctx->h_pinned, sizeof(uint32_t), s));
+    launch_select_topk(b, 1, keep, s);
+    if (check_launch() != YV_OK) return YV_ERR_HIP;
+    YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->det_count, sizeof(int32_t), s));
+    YV_HIP(stage_sync(ctx, s));
+    const int k = ctx->h_pinned[1];
+    if (k > 0) {
+        YV_HIP(stage_d2h(ctx, out_rc, b->det_rc, sizeof(int32_t) * 2 * (size_t)k, s));
+        if (out_resp) YV_HIP(stage_d2h(ctx, out_resp, b->det_resp, sizeof(float) * (size_t)k, s));
+        YV_HIP(stage_sync(ctx, s));
+    }
+    *n_out = k;
     return YV_OK;
 }
 

@@ -135,6 +135,21 @@ void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int
 void launch_match_gated(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
                         int n_bands, const uint2* sorted, const int32_t* band_start, const int32_t* gates, bool mirror,
                         uint32_t* match_key, uint32_t* match_key2, hipStream_t s);
+// Keypoint selection (yv_set_keypoint_select, yavo_select.hip): the filter between the detect kernel and launch_topk.
+// Suppression buckets the corners by tiles of kSelTileRows x kSelTileCols pixels, the quota by the caller's cells; both
+// grids have at most kSelMaxCells cells (the tiles of every accepted H x W do, the cells are the caller's to check).
+constexpr int kSelMaxCells = 8192;
+constexpr int kSelTileRows = 32, kSelTileCols = 64;
+constexpr int kSelMaxRadius = 8;
+constexpr int kSelMaxPerCell = 4096;
+constexpr int kSelMinCell = 8, kSelMaxCell = 8192;
+// Filters cand_keys[img][0 .. cand_count[img]) in place (nms_radius > 0: suppression; per_cell > 0: the quota) and does
+// launch_topk's bookkeeping for the detect kernel's list (cand_seen = corners before the filter, cand_count = 0).
+// scratch: n_images lists of cap keys; starts: [n_images][kSelMaxCells + 1]; counts: [2][n_images].  Returns the array
+// (inside counts) holding the filtered lists' lengths: launch_topk's cand_count, which resets it.
+uint32_t* launch_select(uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, uint32_t* cand_seen, int n_images,
+                        int H, int W, int nms_radius, int cell_rows, int cell_cols, int per_cell, uint64_t* scratch,
+                        int32_t* starts, uint32_t* counts, hipStream_t s);
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
