@@ -172,3 +172,61 @@ def test_match_robust_equals_reference(ctx, nq, nt):
         want["pt1"]["matched"] = 1
         want["pt2"]["matched"] = 1
         np.testing.assert_array_equal(filt, want, err_msg=f"flags {flags} ratio {ratio}")
+
+
+def _match_records(q, t, nn2):
+    """matchFeatures' records from the brute force: the query, its nearest train point's x / y / id, the distance."""
+    m = np.zeros(len(q), yv.MATCH_DTYPE)
+    m["pt1"] = q
+    has = nn2["j1"] >= 0
+    for f in ("x", "y", "id"):
+        m["pt2"][f][has] = t[f][nn2["j1"][has]]
+    m["distance"] = nn2["d1"]
+    return m
+
+
+def _kept_records(m, keep):
+    want = m[keep].copy()
+    want["pt1"]["matched"] = 1
+    want["pt2"]["matched"] = 1
+    return want
+
+
+def test_host_matchers_in_sequence_on_one_context(ctx):
+    """The five host matchers share the single-image workspace and its key buffers: lists that shrink after a larger
+    call (a key left behind past the new nq / nt would surface) on both sides of the 2048 train points between the FP4
+    and the int8 matcher, every result against the brute force of its own inputs."""
+    open_gate = (-65535, 65535, -65535, 65535)
+
+    def check_nn2(got, shape, what):
+        ref, ref_rev = _reference(*shape)
+        nn2, rev = got
+        assert len(nn2) == shape[0] and len(rev) == shape[1]
+        for f in ("d1", "j1", "d2", "j2"):
+            np.testing.assert_array_equal(nn2[f], ref[f], err_msg=f"{what} {f}")
+        np.testing.assert_array_equal(rev, ref_rev, err_msg=f"{what} rev")
+
+    # 1: the filtering finalize with both tests, FP4 in both directions
+    big = (513, 511)
+    q, t = _inputs(*big)
+    nn2, rev = _reference(*big)
+    records = _match_records(q, t, nn2)
+    filt, keep = ctx.match_robust(q, t, THR, ratio=(4, 5), mutual=True)
+    ref_keep = keep_reference(nn2, rev, THR, 3, 4, 5)
+    np.testing.assert_array_equal(keep, ref_keep, err_msg="1 keep")
+    np.testing.assert_array_equal(filt, _kept_records(records, ref_keep), err_msg="1 filtered")
+    # 2: the plain matcher and finalize on far shorter lists
+    small = (33, 2)
+    m = ctx.match_features(*_inputs(*small))
+    np.testing.assert_array_equal(m, _match_records(*_inputs(*small), _reference(*small)[0]), err_msg="2")
+    # 3: int8 forward, FP4 reverse
+    check_nn2(ctx.match_knn2(*_inputs(65, 2049)), (65, 2049), "3")
+    # 4: the gated matcher behind an open gate is the 2-NN matcher
+    check_nn2(ctx.match_gated(*_inputs(*small), open_gate), small, "4")
+    # 5
+    check_nn2(ctx.match_knn2(*_inputs(7, 1)), (7, 1), "5")
+    # 6: back to the first lists through the plain path
+    m = ctx.match_features(q, t)
+    np.testing.assert_array_equal(m, records, err_msg="6 matches")
+    np.testing.assert_array_equal(ctx.filter_matches(m, THR),
+                                  _kept_records(records, keep_reference(nn2, rev, THR, 0, 0, 1)), err_msg="6 filtered")

@@ -474,18 +474,6 @@ int ensure_gates(yv_batch* b, int max_row, int max_col) {
     return YV_OK;
 }
 
-// The gated replacements of launch_match / launch_match_top2 (+ the swapped pairs): the order of every slot, then the
-// matcher over the first n_pairs pairs.  top2 / with_rev need the match filter's buffers.
-void launch_gated_matches(yv_batch* b, int n_pairs, bool top2, bool with_rev, hipStream_t s) {
-    yavo::launch_gate_sort(b->keypoints, b->kp_count, b->nslots, b->max_kp, b->gate_bands, b->gate_cols, b->gate_shift,
-                           b->gate_sorted, b->gate_band, s);
-    yavo::launch_match_gated(b->desc, b->kp_count, b->pairs, n_pairs, b->max_kp, b->gate_bands, b->gate_sorted,
-                             b->gate_band, b->gates, false, b->match_key, top2 ? b->match_key2 : nullptr, s);
-    if (with_rev)
-        yavo::launch_match_gated(b->desc, b->kp_count, b->pairs_rev, n_pairs, b->max_kp, b->gate_bands, b->gate_sorted,
-                                 b->gate_band, b->gates, true, b->rev_key, nullptr, s);
-}
-
 // ---- keypoint selection (yv_set_keypoint_select) ----
 bool select_args_ok(int nms_radius, int cell_rows, int cell_cols, int per_cell) {
     if (nms_radius < 0 || nms_radius > yavo::kSelMaxRadius || per_cell < 0 || per_cell > yavo::kSelMaxPerCell)
@@ -538,6 +526,120 @@ int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
     if (!b->timing || run < 0) return YV_OK;
     if (b->timing == 2 && stage > 1) return YV_OK;  // detect-only: the two events around the detect kernel
     YV_HIP(hipEventRecord(b->events[(size_t)run * kEvPerRun + stage], s));
+    return YV_OK;
+}
+
+// The selection's preflight of a run on H x W images, before any copy or launch: a refused run leaves the batch as it
+// was.
+int prepare_select(yv_batch* b, int H, int W) {
+    if (!select_on(b->ctx)) return YV_OK;
+    if (!select_fits(b->ctx, H, W)) return YV_ERR_CAPACITY;
+    return ensure_select(b);
+}
+
+// One match stage over the batch's first n_pairs pairs (the defaults: the single-image workspace's plain match).
+struct MatchStage {
+    int n_pairs = 1;
+    int max_train = 0, max_train_rev = 0;  // bounds of the train lists' lengths, forward and over the swapped pairs
+                                           // (ungated: <= 2048 selects the FP4 matcher)
+    bool top2 = false;                     // second-best keys and the filtering finalize (ensure_match2 has passed)
+    bool with_rev = false;                 // top2 only: the swapped pairs as well
+    bool gated = false;                    // inside the pairs' gates (ensure_gates has passed, b->gates is set)
+    int thr = 0;                           // removeOutliers' threshold
+    int flags = 0, num = 0, den = 1;       // top2 only: the filter's tests
+    int32_t* kp_count_copy = nullptr;      // optional: the finalize copies kp_count[0, n_slots) there
+    int n_slots = 0;
+};
+
+yavo::MatchLists match_lists(const yv_batch* b) { return {b->desc, b->keypoints, b->kp_count, b->max_kp}; }
+
+yavo::MatchRecords match_records(const yv_batch* b) {
+    return {b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj, b->match_lim};
+}
+
+// The key buffers ([max_pairs][max_kp], 0xFFFFFFFF = no key) hold keys between the stage's matcher and its finalize
+// only; outside a stage every entry is 0xFFFFFFFF:
+// - yv_batch_create fills match_key, ensure_match2 fills match_key2 and rev_key (and the swapped pair list pairs_rev).
+// - A matcher stores a key for every query of every pair, [0, nq): the forward one into match_key (top2: and
+//   match_key2), the one over the swapped pairs, whose queries are the train points, into rev_key [0, nt).
+// - The finalize reads and resets match_key [0, nq); the filtering one also match_key2 [0, nq) and rev_key [0, nt),
+//   whether or not the swapped pairs ran (it then reads "no query" for every train point).
+// So a stage with top2 ends in the filtering finalize and one without in the plain one, and no stage sees the keys of
+// an earlier one, however the lists' lengths changed.  Stage event 4 separates matcher and finalize (run < 0: none).
+int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run) {
+    const yavo::MatchLists lists = match_lists(b);
+    uint32_t* key2 = st.top2 ? b->match_key2 : nullptr;
+    if (st.gated) {
+        yavo::launch_gate_sort(b->keypoints, b->kp_count, b->nslots, b->max_kp, b->gate_bands, b->gate_cols,
+                               b->gate_shift, b->gate_sorted, b->gate_band, s);
+        yavo::launch_match_gated(lists, b->pairs, st.n_pairs, b->gate_bands, b->gate_sorted, b->gate_band, b->gates,
+                                 false, b->match_key, key2, s);
+        if (st.with_rev)
+            yavo::launch_match_gated(lists, b->pairs_rev, st.n_pairs, b->gate_bands, b->gate_sorted, b->gate_band,
+                                     b->gates, true, b->rev_key, nullptr, s);
+    } else {
+        yavo::launch_match(lists, b->pairs, st.n_pairs, st.max_train, b->match_key, key2, s);
+        if (st.with_rev) yavo::launch_match(lists, b->pairs_rev, st.n_pairs, st.max_train_rev, b->rev_key, nullptr, s);
+    }
+    const int rc = record_stage(b, s, run, 4);
+    const yavo::FinalizeRobust rb{b->match_key2, b->rev_key, st.flags, st.num, st.den, b->nn2, b->rev, b->keep};
+    yavo::launch_match_finalize(b->match_key, lists, b->pairs, st.n_pairs, st.thr, match_records(b),
+                                st.top2 ? &rb : nullptr, s, st.kp_count_copy, st.n_slots);
+    return rc;
+}
+
+// One pair of host keypoint lists through the single-image workspace (the matcher does not look at the image size:
+// whatever workspace exists, or a minimal one): the buffers the stage needs, the query list into slot 0, the train list
+// into slot 1 (the carry slot), their counts and packed descriptors, the gate if any, then the stage.
+int match_single_pair(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, MatchStage st,
+                      const int32_t* gate, hipStream_t s) {
+    int rc = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
+    if (rc == YV_OK && st.top2) rc = ensure_match2(ctx->single);
+    // the gated positions come from the caller: all 16 bits
+    if (rc == YV_OK && gate) rc = ensure_gates(ctx->single, yavo::kGateMaxCoord, yavo::kGateMaxCoord);
+    if (rc != YV_OK) return rc;
+    yv_batch* b = ctx->single;
+    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
+    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + (size_t)b->max_kp, t, sizeof(yv_keypoint) * (size_t)nt, s));
+    ctx->h_pinned[0] = nq;
+    ctx->h_pinned[1] = nt;
+    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
+    if (gate) YV_HIP(stage_h2d(ctx, b->gates, gate, 4 * sizeof(int32_t), s));
+    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
+    st.max_train = nt;
+    st.max_train_rev = nq;
+    st.gated = gate != nullptr;
+    (void)match_stage(b, st, s, -1);
+    return check_launch();
+}
+
+// yv_match_knn2's / yv_match_gated's results of the single pair
+int download_nn2(yv_ctx* ctx, yv_match2* out, int nq, int32_t* rev, int nt, hipStream_t s) {
+    YV_HIP(stage_d2h(ctx, out, ctx->single->nn2, sizeof(yv_match2) * (size_t)nq, s));
+    if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, ctx->single->rev, sizeof(int32_t) * (size_t)nt, s));
+    YV_HIP(stage_sync(ctx, s));
+    return YV_OK;
+}
+
+// One array of a counted download: `elem` bytes per counted element from the device's `src` to the caller's `dst`
+// (nullptr: not wanted).
+struct CountedArray {
+    void* dst;
+    const void* src;
+    size_t elem;
+};
+
+// The tail of a host-pointer call: the device's count into the pinned *h_count and a drain (which also lands whatever
+// the caller staged before), then, when the count is positive, that many elements of a and b and a second drain.
+int download_counted(yv_ctx* ctx, int32_t* h_count, const void* d_count, CountedArray a, CountedArray b,
+                     hipStream_t s) {
+    YV_HIP(stage_d2h(ctx, h_count, d_count, sizeof(int32_t), s));
+    YV_HIP(stage_sync(ctx, s));
+    const size_t k = *h_count > 0 ? (size_t)*h_count : 0;
+    if (k == 0) return YV_OK;
+    if (a.dst) YV_HIP(stage_d2h(ctx, a.dst, a.src, a.elem * k, s));
+    if (b.dst) YV_HIP(stage_d2h(ctx, b.dst, b.src, b.elem * k, s));
+    YV_HIP(stage_sync(ctx, s));
     return YV_OK;
 }
 
@@ -952,11 +1054,8 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
     const int H = b->H, W = b->W, K = b->max_kp;
     const int keep = std::min(ctx->max_corners, K);
-    if (select_on(ctx)) {  // before any copy or launch: a refused run leaves the batch as it was
-        if (!select_fits(ctx, H, W)) return YV_ERR_CAPACITY;
-        const int st = ensure_select(b);
-        if (st != YV_OK) return st;
-    }
+    const int sel = prepare_select(b, H, W);
+    if (sel != YV_OK) return sel;
     if (b->pending_carry >= 0 && join_build(b, s) != YV_OK) return YV_ERR_HIP;
     if (b->pending_carry >= 0) {
         const size_t c = (size_t)b->pending_carry, dst = (size_t)b->max_images, nk = (size_t)K;
@@ -993,28 +1092,21 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     // the asynchronous edge build reads a copy of the keypoint counts (the next run's top-K rewrites them):
     // the finalize kernel writes it, where a separate device copy waited ~50 us for a CU at the end of the step
     const bool copy_counts = b->n_pairs > 0 && b->overlap && b->build_async && b->lk_step == 0;
-    if (b->run_flags != 0) {
-        // the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
-        if (b->gated) {
-            launch_gated_matches(b, b->n_pairs, true, (b->match_flags & YV_MATCH_MUTUAL) != 0, s);
-        } else {
-            yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, b->match_key2, s);
-            if (b->match_flags & YV_MATCH_MUTUAL)
-                yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, b->n_pairs, K, K, b->rev_key, s);
-        }
-        rc |= record_stage(b, s, run, 4);
-        yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs,
-                                           b->n_pairs, K, match_thr, b->match_flags, b->ratio_num, b->ratio_den,
-                                           b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj,
-                                           b->match_lim, b->nn2, b->rev, b->keep, s,
-                                           copy_counts ? b->kp_count_build : nullptr, b->nslots);
-    } else if (b->n_pairs > 0) {
-        if (b->gated) launch_gated_matches(b, b->n_pairs, false, false, s);
-        else yavo::launch_match(b->desc, b->kp_count, b->pairs, b->n_pairs, K, K, b->match_key, s);
-        rc |= record_stage(b, s, run, 4);
-        yavo::launch_match_finalize(b->match_key, b->keypoints, b->kp_count, b->pairs, b->n_pairs, K, match_thr,
-                                    b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj,
-                                    b->match_lim, s, copy_counts ? b->kp_count_build : nullptr, b->nslots);
+    if (b->n_pairs > 0) {
+        // with the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
+        MatchStage st;
+        st.n_pairs = b->n_pairs;
+        st.max_train = st.max_train_rev = K;
+        st.top2 = b->run_flags != 0;
+        st.with_rev = st.top2 && (b->match_flags & YV_MATCH_MUTUAL) != 0;
+        st.gated = b->gated;
+        st.thr = match_thr;
+        st.flags = b->match_flags;
+        st.num = b->ratio_num;
+        st.den = b->ratio_den;
+        st.kp_count_copy = copy_counts ? b->kp_count_build : nullptr;
+        st.n_slots = b->nslots;
+        rc |= match_stage(b, st, s, run);
     } else {
         rc |= record_stage(b, s, run, 4);
     }
@@ -1446,26 +1538,18 @@ int yv_detect(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, int max
     yv_batch* b = ctx->single;
     hipStream_t s = ctx->stream;
     const int keep = std::min(std::min(ctx->max_corners, max_kp), b->max_kp);
-    if (select_on(ctx)) {
-        if (!select_fits(ctx, H, W)) return YV_ERR_CAPACITY;
-        st = ensure_select(b);
-        if (st != YV_OK) return st;
-    }
+    st = prepare_select(b, H, W);
+    if (st != YV_OK) return st;
     if (upload_image(b, img, stride, s) != YV_OK) return YV_ERR_HIP;
     yavo::launch_fast_harris(b->staging, 1, H, W, W, (int64_t)H * W, ctx->fast_thr, ctx->harris_eigen, b->cand_keys, b->cap,
                              b->cand_count, s);
     launch_select_topk(b, 1, keep, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->det_count, sizeof(int32_t), s));
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->cand_seen, sizeof(uint32_t), s));
-    YV_HIP(stage_sync(ctx, s));
-    const int k = ctx->h_pinned[0];
-    if (k > 0) {
-        YV_HIP(stage_d2h(ctx, rc, b->det_rc, sizeof(int32_t) * 2 * (size_t)k, s));
-        if (resp) YV_HIP(stage_d2h(ctx, resp, b->det_resp, sizeof(float) * (size_t)k, s));
-        YV_HIP(stage_sync(ctx, s));
-    }
-    *n = k;
+    YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->cand_seen, sizeof(uint32_t), s));  // lands with the count
+    st = download_counted(ctx, ctx->h_pinned, b->det_count, {rc, b->det_rc, 2 * sizeof(int32_t)},
+                          {resp, b->det_resp, sizeof(float)}, s);
+    if (st != YV_OK) return st;
+    *n = ctx->h_pinned[0];
     if (n_candidates) *n_candidates = ctx->h_pinned[1];
     return YV_OK;
 }
@@ -1483,10 +1567,8 @@ int yv_select_corners(yv_ctx* ctx, int H, int W, const int32_t* rc, const float*
     int st = ensure_single(ctx, H, W);
     if (st != YV_OK) return st;
     yv_batch* b = ctx->single;
-    if (select_on(ctx)) {
-        st = ensure_select(b);
-        if (st != YV_OK) return st;
-    }
+    st = prepare_select(b, H, W);  // the cells fit (tested above, before the device was touched)
+    if (st != YV_OK) return st;
     hipStream_t s = ctx->stream;
     const int keep = std::min(std::min(ctx->max_corners, max_kp), b->max_kp);
     // the detect kernel's key, from the response's bits as they are: (~ord) << 32 | row * W + col
@@ -1505,15 +1587,10 @@ int yv_select_corners(yv_ctx* ctx, int H, int W, const int32_t* rc, const float*
     YV_HIP(stage_h2d(ctx, b->cand_count, ctx->h_pinned, sizeof(uint32_t), s));
     launch_select_topk(b, 1, keep, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned + 1, b->det_count, sizeof(int32_t), s));
-    YV_HIP(stage_sync(ctx, s));
-    const int k = ctx->h_pinned[1];
-    if (k > 0) {
-        YV_HIP(stage_d2h(ctx, out_rc, b->det_rc, sizeof(int32_t) * 2 * (size_t)k, s));
-        if (out_resp) YV_HIP(stage_d2h(ctx, out_resp, b->det_resp, sizeof(float) * (size_t)k, s));
-        YV_HIP(stage_sync(ctx, s));
-    }
-    *n_out = k;
+    st = download_counted(ctx, ctx->h_pinned + 1, b->det_count, {out_rc, b->det_rc, 2 * sizeof(int32_t)},
+                          {out_resp, b->det_resp, sizeof(float)}, s);
+    if (st != YV_OK) return st;
+    *n_out = ctx->h_pinned[1];
     return YV_OK;
 }
 
@@ -1539,14 +1616,9 @@ int yv_describe(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const
     yavo::launch_brief(b->blur, 1, H, W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, b->max_kp, b->keypoints,
                        b->desc, b->brief_loff, new_loff, b->brief_heads, brief_workers(ctx, W), s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned + 2, b->kp_count, sizeof(int32_t), s));
-    YV_HIP(stage_sync(ctx, s));
-    const int m = ctx->h_pinned[2];
-    if (m > 0) {
-        YV_HIP(stage_d2h(ctx, out, b->keypoints, sizeof(yv_keypoint) * (size_t)m, s));
-        YV_HIP(stage_sync(ctx, s));
-    }
-    *n_out = m;
+    st = download_counted(ctx, ctx->h_pinned + 2, b->kp_count, {out, b->keypoints, sizeof(yv_keypoint)}, {}, s);
+    if (st != YV_OK) return st;
+    *n_out = ctx->h_pinned[2];
     return YV_OK;
 }
 
@@ -1556,23 +1628,10 @@ int yv_match_features(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoi
     if (nq == 0) return YV_OK;
     if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
     StageScope stage_scope(ctx);
-    // the matcher does not look at the image size: reuse whatever workspace exists (or a minimal one)
-    int st = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
-    if (st != YV_OK) return st;
-    yv_batch* b = ctx->single;
     hipStream_t s = ctx->stream;
-    const size_t nk = (size_t)b->max_kp;
-    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
-    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + nk, t, sizeof(yv_keypoint) * (size_t)nt, s));
-    ctx->h_pinned[0] = nq;
-    ctx->h_pinned[1] = nt;
-    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
-    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
-    yavo::launch_match(b->desc, b->kp_count, b->pairs, 1, b->max_kp, nt, b->match_key, s);
-    yavo::launch_match_finalize(b->match_key, b->keypoints, b->kp_count, b->pairs, 1, b->max_kp, 0, b->matches,
-                                b->match_count, b->filtered, b->filt_count, b->match_dj, b->match_lim, s);
-    if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, out, b->matches, sizeof(yv_match) * (size_t)nq, s));
+    const int st = match_single_pair(ctx, q, nq, t, nt, MatchStage{}, nullptr, s);
+    if (st != YV_OK) return st;
+    YV_HIP(stage_d2h(ctx, out, ctx->single->matches, sizeof(yv_match) * (size_t)nq, s));
     YV_HIP(stage_sync(ctx, s));
     return YV_OK;
 }
@@ -1591,42 +1650,11 @@ int yv_filter_matches(yv_ctx* ctx, const yv_match* in, int n, int thr, yv_match*
     YV_HIP(stage_h2d(ctx, b->matches, in, sizeof(yv_match) * (size_t)n, s));
     yavo::launch_filter_records(b->matches, n, thr, b->filtered, b->filt_count, s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->filt_count, sizeof(int32_t), s));
-    YV_HIP(stage_sync(ctx, s));
-    const int m = ctx->h_pinned[0];
-    if (m > 0) {
-        YV_HIP(stage_d2h(ctx, out, b->filtered, sizeof(yv_match) * (size_t)m, s));
-        YV_HIP(stage_sync(ctx, s));
-    }
-    *n_out = m;
+    st = download_counted(ctx, ctx->h_pinned, b->filt_count, {out, b->filtered, sizeof(yv_match)}, {}, s);
+    if (st != YV_OK) return st;
+    *n_out = ctx->h_pinned[0];
     return YV_OK;
 }
-
-namespace {
-// uploads both keypoint lists into the single-image workspace (query = slot 0, train = slot 1), packs their
-// descriptors and runs the filtered match of its one pair
-int match2_single(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags, int num,
-                  int den, bool with_rev, hipStream_t s) {
-    int st = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
-    if (st != YV_OK) return st;
-    yv_batch* b = ctx->single;
-    st = ensure_match2(b);
-    if (st != YV_OK) return st;
-    const size_t nk = (size_t)b->max_kp;
-    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
-    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + nk, t, sizeof(yv_keypoint) * (size_t)nt, s));
-    ctx->h_pinned[0] = nq;
-    ctx->h_pinned[1] = nt;
-    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
-    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
-    yavo::launch_match_top2(b->desc, b->kp_count, b->pairs, 1, b->max_kp, nt, b->match_key, b->match_key2, s);
-    if (with_rev) yavo::launch_match(b->desc, b->kp_count, b->pairs_rev, 1, b->max_kp, nq, b->rev_key, s);
-    yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs, 1,
-                                       b->max_kp, thr, flags, num, den, b->matches, b->match_count, b->filtered,
-                                       b->filt_count, b->match_dj, b->match_lim, b->nn2, b->rev, b->keep, s);
-    return check_launch();
-}
-}  // namespace
 
 int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, yv_match2* out,
                   int32_t* rev) {
@@ -1641,13 +1669,11 @@ int yv_match_knn2(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* 
     if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
     StageScope stage_scope(ctx);
     hipStream_t s = ctx->stream;
-    const int st = match2_single(ctx, q, nq, t, nt, 0, 0, 0, 1, rev != nullptr, s);
-    if (st != YV_OK) return st;
-    yv_batch* b = ctx->single;
-    YV_HIP(stage_d2h(ctx, out, b->nn2, sizeof(yv_match2) * (size_t)nq, s));
-    if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, b->rev, sizeof(int32_t) * (size_t)nt, s));
-    YV_HIP(stage_sync(ctx, s));
-    return YV_OK;
+    MatchStage stage;
+    stage.top2 = true;
+    stage.with_rev = rev != nullptr;
+    const int st = match_single_pair(ctx, q, nq, t, nt, stage, nullptr, s);
+    return st != YV_OK ? st : download_nn2(ctx, out, nq, rev, nt, s);
 }
 
 int yv_match_gated(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, const int32_t gate[4],
@@ -1669,30 +1695,11 @@ int yv_match_gated(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint*
     if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
     StageScope stage_scope(ctx);
     hipStream_t s = ctx->stream;
-    int st = ctx->single ? YV_OK : ensure_single(ctx, 16, 16);
-    if (st != YV_OK) return st;
-    yv_batch* b = ctx->single;
-    st = ensure_match2(b);
-    if (st != YV_OK) return st;
-    st = ensure_gates(b, yavo::kGateMaxCoord, yavo::kGateMaxCoord);  // positions come from the caller: all 16 bits
-    if (st != YV_OK) return st;
-    const size_t nk = (size_t)b->max_kp;
-    YV_HIP(stage_h2d(ctx, b->keypoints, q, sizeof(yv_keypoint) * (size_t)nq, s));
-    if (nt > 0) YV_HIP(stage_h2d(ctx, b->keypoints + nk, t, sizeof(yv_keypoint) * (size_t)nt, s));
-    ctx->h_pinned[0] = nq;
-    ctx->h_pinned[1] = nt;
-    YV_HIP(stage_h2d(ctx, b->kp_count, ctx->h_pinned, 2 * sizeof(int32_t), s));
-    YV_HIP(stage_h2d(ctx, b->gates, gate, 4 * sizeof(int32_t), s));
-    yavo::launch_pack_desc(b->keypoints, b->kp_count, 2, b->max_kp, b->desc, s);
-    launch_gated_matches(b, 1, true, rev != nullptr, s);
-    yavo::launch_match_finalize_robust(b->match_key, b->match_key2, b->rev_key, b->keypoints, b->kp_count, b->pairs, 1,
-                                       b->max_kp, 0, 0, 0, 1, b->matches, b->match_count, b->filtered, b->filt_count,
-                                       b->match_dj, b->match_lim, b->nn2, b->rev, b->keep, s);
-    if (check_launch() != YV_OK) return YV_ERR_HIP;
-    YV_HIP(stage_d2h(ctx, out, b->nn2, sizeof(yv_match2) * (size_t)nq, s));
-    if (rev && nt > 0) YV_HIP(stage_d2h(ctx, rev, b->rev, sizeof(int32_t) * (size_t)nt, s));
-    YV_HIP(stage_sync(ctx, s));
-    return YV_OK;
+    MatchStage stage;
+    stage.top2 = true;
+    stage.with_rev = rev != nullptr;
+    const int st = match_single_pair(ctx, q, nq, t, nt, stage, gate, s);
+    return st != YV_OK ? st : download_nn2(ctx, out, nq, rev, nt, s);
 }
 
 int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint* t, int nt, int thr, int flags,
@@ -1708,19 +1715,20 @@ int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint
     StageScope stage_scope(ctx);
     hipStream_t s = ctx->stream;
     const bool ratio = (flags & YV_MATCH_RATIO) != 0;
-    const int st = match2_single(ctx, q, nq, t, nt, thr, flags, ratio ? ratio_num : 0, ratio ? ratio_den : 1,
-                                 (flags & YV_MATCH_MUTUAL) != 0, s);
+    MatchStage stage;
+    stage.top2 = true;
+    stage.with_rev = (flags & YV_MATCH_MUTUAL) != 0;
+    stage.thr = thr;
+    stage.flags = flags;
+    stage.num = ratio ? ratio_num : 0;
+    stage.den = ratio ? ratio_den : 1;
+    int st = match_single_pair(ctx, q, nq, t, nt, stage, nullptr, s);
     if (st != YV_OK) return st;
-    yv_batch* b = ctx->single;
-    YV_HIP(stage_d2h(ctx, ctx->h_pinned, b->filt_count, sizeof(int32_t), s));
-    if (keep) YV_HIP(stage_d2h(ctx, keep, b->keep, (size_t)nq, s));
-    YV_HIP(stage_sync(ctx, s));
-    const int m = ctx->h_pinned[0];
-    if (m > 0) {
-        YV_HIP(stage_d2h(ctx, out, b->filtered, sizeof(yv_match) * (size_t)m, s));
-        YV_HIP(stage_sync(ctx, s));
-    }
-    *n_out = m;
+    const yv_batch* b = ctx->single;
+    if (keep) YV_HIP(stage_d2h(ctx, keep, b->keep, (size_t)nq, s));  // lands with the count
+    st = download_counted(ctx, ctx->h_pinned, b->filt_count, {out, b->filtered, sizeof(yv_match)}, {}, s);
+    if (st != YV_OK) return st;
+    *n_out = ctx->h_pinned[0];
     return YV_OK;
 }
 

@@ -93,32 +93,49 @@ void launch_brief(const uint8_t* blur, int n_images, int H, int W, const int8_t*
 // Pack KeyPoint records -> descriptors (host-supplied keypoints).
 void launch_pack_desc(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp,
                       Desc* desc, hipStream_t s);
+// The keypoint lists a matcher reads: slot i holds kp_count[i] points at desc / keypoints[i * max_kp].
+struct MatchLists {
+    const Desc* desc;
+    const yv_keypoint* keypoints;
+    const int32_t* kp_count;
+    int max_kp;
+};
+// The finalize's outputs per pair: all records and the kept ones ([pair][max_kp]) with their counts, every query's
+// {distance, train index} and the removeOutliers limit.
+struct MatchRecords {
+    yv_match* matches;
+    int32_t* match_count;
+    yv_match* filtered;
+    int32_t* filt_count;
+    int2* match_dj;
+    int32_t* match_lim;
+};
 // Brute-force Hamming NN: match_key[pair][q] = min over t of (dist << 16 | t).  max_train bounds every train
-// list's length (<= 2048: the FP4 matcher, otherwise the int8 +-1 form); max_kp is the slot stride.
-void launch_match(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs,
-                  int max_kp, int max_train, uint32_t* match_key, hipStream_t s);
-// Matches records (matchFeatures) + removeOutliers per pair.  match_key entries are reset to
-// 0xFFFFFFFF after they are read (ready for the next match).
-void launch_match_finalize(uint32_t* match_key, const yv_keypoint* keypoints,
-                           const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                           int thr, yv_match* matches, int32_t* match_count, yv_match* filtered,
-                           int32_t* filt_count, int2* match_dj, int32_t* match_lim, hipStream_t s,
-                           int32_t* kp_count_copy = nullptr, int n_slots = 0);  // + kp_count[0, n_slots) -> copy
+// list's length (<= 2048: the FP4 matcher, otherwise the int8 +-1 form).  match_key2 != nullptr: also every query's
+// second-best key there (same format, 0xFFFFFFFF: no second train point), exact, first index on ties.
+void launch_match(const MatchLists& lists, const int32_t* pairs, int n_pairs, int max_train, uint32_t* match_key,
+                  uint32_t* match_key2, hipStream_t s);
 // The 2-NN match filter (yv_batch_set_match_filter; the values of YV_MATCH_RATIO / YV_MATCH_MUTUAL).
 constexpr int kMatchRatio = 1, kMatchMutual = 2;
-// launch_match that also keeps every query's second-best key (same format, 0xFFFFFFFF: no second train point) in
-// match_key2: exact, first index on ties.
-void launch_match_top2(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                       int max_train, uint32_t* match_key, uint32_t* match_key2, hipStream_t s);
-// launch_match_finalize with the filter: consumes (and resets) match_key, match_key2 and rev_key (the matcher's keys
-// of the swapped pairs; untouched 0xFFFFFFFF entries read as "no query"); a query is kept iff distance < limit and
-// the tests in `flags` pass.  Writes nn2[pair][i] = {d1, j1, d2, j2}, rev[pair][j] and keep[pair][i] as well.
-void launch_match_finalize_robust(uint32_t* match_key, uint32_t* match_key2, uint32_t* rev_key,
-                                  const yv_keypoint* keypoints, const int32_t* kp_count, const int32_t* pairs,
-                                  int n_pairs, int max_kp, int thr, int flags, int ratio_num, int ratio_den,
-                                  yv_match* matches, int32_t* match_count, yv_match* filtered, int32_t* filt_count,
-                                  int2* match_dj, int32_t* match_lim, int4* nn2, int32_t* rev, uint8_t* keep,
-                                  hipStream_t s, int32_t* kp_count_copy = nullptr, int n_slots = 0);
+// ROBUST (the 2-NN match filter): also consumes the second-best keys and the reverse direction's keys (rev_key[pair][j]
+// = train point j's best query, from the matcher run on the swapped pair), and keeps a query iff
+//   d1 < lim  &&  (no YV_MATCH_RATIO || d1 * den < d2 * num in int64)  &&  (no YV_MATCH_MUTUAL || i1(j1) == i).
+// matches / match_dj / match_lim are written as without it; filtered / filt_count hold the kept records only; nn2 =
+// {d1, j1, d2, j2}, rev = i1(j) (-1: not computed or no query), keep = one byte per query.
+struct FinalizeRobust {
+    uint32_t* match_key2;
+    uint32_t* rev_key;
+    int flags, num, den;
+    int4* nn2;
+    int32_t* rev;
+    uint8_t* keep;
+};
+// Matches records (matchFeatures) + removeOutliers per pair.  match_key entries are reset to 0xFFFFFFFF after they are
+// read (ready for the next match).  rb != nullptr: with the filter, which consumes (and resets) rb->match_key2 and
+// rb->rev_key as well (untouched 0xFFFFFFFF entries read as "no query").  kp_count_copy: + kp_count[0, n_slots) -> copy.
+void launch_match_finalize(uint32_t* match_key, const MatchLists& lists, const int32_t* pairs, int n_pairs, int thr,
+                           const MatchRecords& out, const FinalizeRobust* rb, hipStream_t s,
+                           int32_t* kp_count_copy = nullptr, int n_slots = 0);
 // The gated matcher (yv_match_gated / yv_batch_set_match_gates, yavo_match_gate.hip).  Per slot, the keypoints
 // bucketed by cell = (band of kGateBandRows rows, column >> col_shift): sorted[slot][max_kp] = {row | column << 16,
 // keypoint index} cell by cell, band_start[slot][n_bands + 1] = first entry of every band.  n_bands * kGateBandRows
@@ -129,12 +146,12 @@ constexpr int kGateMaxCells = 8192;
 constexpr int kGateMaxCoord = 65535;
 void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp, int n_bands,
                       int col_cells, int col_shift, uint2* sorted, int32_t* band_start, hipStream_t s);
-// launch_match / launch_match_top2 (match_key2 != nullptr) over the train points inside each pair's gate: gates[pair]
-// = {drow_lo, drow_hi, dcol_lo, dcol_hi} on train minus query position; mirror: the gate of the swapped pair list.
-// Writes a key for every query of every pair, 0xFFFFFFFF where the gate holds no (second) train point.
-void launch_match_gated(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                        int n_bands, const uint2* sorted, const int32_t* band_start, const int32_t* gates, bool mirror,
-                        uint32_t* match_key, uint32_t* match_key2, hipStream_t s);
+// launch_match over the train points inside each pair's gate: gates[pair] = {drow_lo, drow_hi, dcol_lo, dcol_hi} on
+// train minus query position; mirror: the gate of the swapped pair list.  Writes a key for every query of every pair,
+// 0xFFFFFFFF where the gate holds no (second) train point.
+void launch_match_gated(const MatchLists& lists, const int32_t* pairs, int n_pairs, int n_bands, const uint2* sorted,
+                        const int32_t* band_start, const int32_t* gates, bool mirror, uint32_t* match_key,
+                        uint32_t* match_key2, hipStream_t s);
 // Keypoint selection (yv_set_keypoint_select, yavo_select.hip): the filter between the detect kernel and launch_topk.
 // Suppression buckets the corners by tiles of kSelTileRows x kSelTileCols pixels, the quota by the caller's cells; both
 // grids have at most kSelMaxCells cells (the tiles of every accepted H x W do, the cells are the caller's to check).

@@ -1782,36 +1782,31 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, 8))) v
 
 namespace {
 template <int QT, int WPE, bool TOP2>
-void launch_fp4(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                uint32_t* match_key, uint32_t* match_key2, hipStream_t s) {
+void launch_fp4(const MatchLists& lists, const int32_t* pairs, int n_pairs, uint32_t* match_key, uint32_t* match_key2,
+                hipStream_t s) {
     constexpr int QB = 4 * QT * 32;
-    dim3 grid((max_kp + QB - 1) / QB, n_pairs);
-    hipLaunchKernelGGL((match_fp4_kernel<QT, WPE, TOP2>), grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp,
-                       match_key, match_key2);
+    dim3 grid((lists.max_kp + QB - 1) / QB, n_pairs);
+    hipLaunchKernelGGL((match_fp4_kernel<QT, WPE, TOP2>), grid, dim3(256), 0, s, lists.desc, lists.kp_count, pairs,
+                       lists.max_kp, match_key, match_key2);
 }
 }  // namespace
 
-void launch_match(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                  int max_train, uint32_t* match_key, hipStream_t s) {
+void launch_match(const MatchLists& lists, const int32_t* pairs, int n_pairs, int max_train, uint32_t* match_key,
+                  uint32_t* match_key2, hipStream_t s) {
     if (max_train > 2048) {
-        dim3 grid((max_kp + MM_QB - 1) / MM_QB, n_pairs);
-        hipLaunchKernelGGL(match_kernel, grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp, match_key);
+        dim3 grid((lists.max_kp + MM_QB - 1) / MM_QB, n_pairs);
+        if (match_key2)
+            hipLaunchKernelGGL(match_top2_kernel, grid, dim3(256), 0, s, lists.desc, lists.kp_count, pairs,
+                               lists.max_kp, match_key, match_key2);
+        else
+            hipLaunchKernelGGL(match_kernel, grid, dim3(256), 0, s, lists.desc, lists.kp_count, pairs, lists.max_kp,
+                               match_key);
         return;
     }
-    // FP4: 4 query tiles of 32 per wave, 3 waves per SIMD (168 VGPRs; 2 tiles at 4 waves per SIMD: 1.60 ms vs 1.43,
-    // profiles/r06/c14)
-    launch_fp4<4, 3, false>(desc, kp_count, pairs, n_pairs, max_kp, match_key, nullptr, s);
-}
-
-void launch_match_top2(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                       int max_train, uint32_t* match_key, uint32_t* match_key2, hipStream_t s) {
-    if (max_train > 2048) {
-        dim3 grid((max_kp + MM_QB - 1) / MM_QB, n_pairs);
-        hipLaunchKernelGGL(match_top2_kernel, grid, dim3(256), 0, s, desc, kp_count, pairs, max_kp, match_key,
-                           match_key2);
-        return;
-    }
-    launch_fp4<MF2_QT, MF2_WPE, true>(desc, kp_count, pairs, n_pairs, max_kp, match_key, match_key2, s);
+    // FP4, best key only: 4 query tiles of 32 per wave, 3 waves per SIMD (168 VGPRs; 2 tiles at 4 waves per SIMD: 1.60 ms
+    // vs 1.43, profiles/r06/c14)
+    if (!match_key2) launch_fp4<4, 3, false>(lists, pairs, n_pairs, match_key, nullptr, s);
+    else launch_fp4<MF2_QT, MF2_WPE, true>(lists, pairs, n_pairs, match_key, match_key2, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1837,20 +1832,7 @@ __device__ __forceinline__ int outlier_limit(int min_d, int thr) {
     return twice > thr ? twice : thr;
 }
 
-// ROBUST (the 2-NN match filter): also consumes the second-best keys and the reverse direction's keys (rev_key[pair][j]
-// = train point j's best query, from the matcher run on the swapped pair), and keeps a query iff
-//   d1 < lim  &&  (no YV_MATCH_RATIO || d1 * den < d2 * num in int64)  &&  (no YV_MATCH_MUTUAL || i1(j1) == i).
-// matches / match_dj / match_lim are written as without it; filtered / filt_count hold the kept records only; nn2 =
-// {d1, j1, d2, j2}, rev = i1(j) (-1: not computed or no query), keep = one byte per query.
-struct FinalizeRobust {
-    uint32_t* match_key2;
-    uint32_t* rev_key;
-    int flags, num, den;
-    int4* nn2;
-    int32_t* rev;
-    uint8_t* keep;
-};
-
+// ROBUST: the 2-NN match filter over rb (FinalizeRobust, yavo_internal.h)
 template <bool ROBUST>
 __global__ __launch_bounds__(FZ_NT) void match_finalize_kernel(
     uint32_t* __restrict__ match_key, const yv_keypoint* __restrict__ keypoints,
@@ -1979,25 +1961,13 @@ __global__ __launch_bounds__(FZ_NT) void match_finalize_kernel(
     }
 }
 
-void launch_match_finalize(uint32_t* match_key, const yv_keypoint* keypoints, const int32_t* kp_count,
-                           const int32_t* pairs, int n_pairs, int max_kp, int thr, yv_match* matches,
-                           int32_t* match_count, yv_match* filtered, int32_t* filt_count, int2* match_dj,
-                           int32_t* match_lim, hipStream_t s, int32_t* kp_count_copy, int n_slots) {
-    hipLaunchKernelGGL(match_finalize_kernel<false>, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, keypoints, kp_count,
-                       pairs, max_kp, thr, matches, match_count, filtered, filt_count, match_dj, match_lim,
-                       kp_count_copy, n_slots, FinalizeRobust{});
-}
-
-void launch_match_finalize_robust(uint32_t* match_key, uint32_t* match_key2, uint32_t* rev_key,
-                                  const yv_keypoint* keypoints, const int32_t* kp_count, const int32_t* pairs,
-                                  int n_pairs, int max_kp, int thr, int flags, int ratio_num, int ratio_den,
-                                  yv_match* matches, int32_t* match_count, yv_match* filtered, int32_t* filt_count,
-                                  int2* match_dj, int32_t* match_lim, int4* nn2, int32_t* rev, uint8_t* keep,
-                                  hipStream_t s, int32_t* kp_count_copy, int n_slots) {
-    const FinalizeRobust rb{match_key2, rev_key, flags, ratio_num, ratio_den, nn2, rev, keep};
-    hipLaunchKernelGGL(match_finalize_kernel<true>, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, keypoints, kp_count,
-                       pairs, max_kp, thr, matches, match_count, filtered, filt_count, match_dj, match_lim,
-                       kp_count_copy, n_slots, rb);
+void launch_match_finalize(uint32_t* match_key, const MatchLists& lists, const int32_t* pairs, int n_pairs, int thr,
+                           const MatchRecords& out, const FinalizeRobust* rb, hipStream_t s, int32_t* kp_count_copy,
+                           int n_slots) {
+    const auto kernel = !rb ? match_finalize_kernel<false> : match_finalize_kernel<true>;
+    hipLaunchKernelGGL(kernel, dim3(n_pairs), dim3(FZ_NT), 0, s, match_key, lists.keypoints, lists.kp_count, pairs,
+                       lists.max_kp, thr, out.matches, out.match_count, out.filtered, out.filt_count, out.match_dj,
+                       out.match_lim, kp_count_copy, n_slots, rb ? *rb : FinalizeRobust{});
 }
 
 // removeOutliers over a caller-supplied Matches list (n <= kMaxKp), one workgroup.

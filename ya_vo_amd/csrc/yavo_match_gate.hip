@@ -244,18 +244,15 @@ void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int
                        col_cells, col_shift, sorted, band_start);
 }
 
-void launch_match_gated(const Desc* desc, const int32_t* kp_count, const int32_t* pairs, int n_pairs, int max_kp,
-                        int n_bands, const uint2* sorted, const int32_t* band_start, const int32_t* gates, bool mirror,
-                        uint32_t* match_key, uint32_t* match_key2, hipStream_t s) {
+void launch_match_gated(const MatchLists& lists, const int32_t* pairs, int n_pairs, int n_bands, const uint2* sorted,
+                        const int32_t* band_start, const int32_t* gates, bool mirror, uint32_t* match_key,
+                        uint32_t* match_key2, hipStream_t s) {
     constexpr int per_block = (GM_NT / 64) * GM_Q;
-    dim3 grid((max_kp + per_block - 1) / per_block, n_pairs);
+    dim3 grid((lists.max_kp + per_block - 1) / per_block, n_pairs);
     const int4* g = reinterpret_cast<const int4*>(gates);
-    if (match_key2)
-        hipLaunchKernelGGL(match_gated_kernel<true>, grid, dim3(GM_NT), 0, s, desc, kp_count, pairs, max_kp, n_bands,
-                           sorted, band_start, g, mirror ? 1 : 0, match_key, match_key2);
-    else
-        hipLaunchKernelGGL(match_gated_kernel<false>, grid, dim3(GM_NT), 0, s, desc, kp_count, pairs, max_kp, n_bands,
-                           sorted, band_start, g, mirror ? 1 : 0, match_key, nullptr);
+    const auto kernel = match_key2 ? match_gated_kernel<true> : match_gated_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(GM_NT), 0, s, lists.desc, lists.kp_count, pairs, lists.max_kp, n_bands,
+                       sorted, band_start, g, mirror ? 1 : 0, match_key, match_key2);
 }
 
 }  // namespace yavo
