@@ -211,7 +211,8 @@ int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates /* [4 * n_pairs] 
  * (src/LoopHandler.cc:867-885, left camera = world, right camera pose T_right; accepted iff success and
  * Z > 0 as in triangulate2View :658-726), measurement = the frame-(k-1) keypoint (x, y).  The pose of
  * frame k-1 in frame k's camera is then LoopHandler::optimizePoseOnly (:730-861) from the prior.  K and
- * T_right are copied once; tracks are validated against the pairs (YV_ERR_INVALID otherwise). */
+ * T_right are copied once; tracks are validated against the pairs (YV_ERR_INVALID otherwise), and a NaN or infinite
+ * entry of K or T_right is YV_ERR_INVALID as well. */
 int yv_batch_set_tracks(yv_batch* b, const int32_t* tracks /* [2*n_tracks] */, int n_tracks, const double K[9],
                         const double T_right[7]);
 /* Build the track edges and solve every track's pose in one launch each (asynchronous on `stream`, NULL =

@@ -41,7 +41,8 @@ int yv_world2camera(struct yv_ctx* ctx, const double* X, int n, const double pos
 /* LoopHandler::optimizePoseOnly (src/LoopHandler.cc:730-861) with the g2o edge of include/Optimizer.hpp:40-135:
  * pose-only Levenberg-Marquardt from the prior `pose`, 4 rounds x optimize(10), Huber(1) kernel (removed after
  * round 3), chi2 > 5.991 -> outlier.  X [n][3] world points, uv [n][2] measurements (kp.x, kp.y).  pose is
- * updated in place; outlier [n] = final flags; *inliers = n - outliers.  n <= 4096. */
+ * updated in place; outlier [n] = final flags; *inliers = n - outliers.  n <= 4096 (YV_ERR_CAPACITY past it); a prior
+ * with a NaN or infinite entry is YV_ERR_INVALID (yv_pose_gn the same). */
 int yv_pose_lm(struct yv_ctx* ctx, const double* X, const double* uv, int n, const double K[9], double pose[7],
                uint8_t* outlier, int* inliers);
 
@@ -51,7 +52,11 @@ int yv_pose_gn(struct yv_ctx* ctx, const double* X, const double* uv, int n, con
                int* iterations);
 
 /* Batched device-pointer forms (asynchronous on `stream`, NULL = context stream).  Problem p owns edges
- * [d_offsets[p], d_offsets[p+1]) of d_X [][3] / d_uv [][2]; d_K [p][9]; d_poses [p][7] in/out. */
+ * [d_offsets[p], d_offsets[p+1]) of d_X [][3] / d_uv [][2]; d_K [p][9]; d_poses [p][7] in/out.
+ * yv_pose_lm_batch solves a problem of more than 4096 edges on its first 4096 alone (no error: the call does not see
+ * the offsets): the pose and d_outlier flags are those of that shorter problem, d_inliers[p] = 4096 - its outliers,
+ * and the problem's d_outlier bytes past the first 4096 are left untouched.  Priors, points and measurements are not
+ * checked: non-finite ones give the reference's result on them (usually the prior back, or a NaN pose). */
 int yv_pose_lm_batch(struct yv_ctx* ctx, int n_problems, const int32_t* d_offsets, const double* d_X,
                      const double* d_uv, const double* d_K, double* d_poses, uint8_t* d_outlier,
                      int32_t* d_inliers, void* stream);

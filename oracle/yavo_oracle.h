@@ -149,6 +149,32 @@ int or_pose_lm(const double* X, const double* uv, int n, const double* K, double
 /* Pose-LM diagnostics: {builds, trials, accepted trials} since the last reset. */
 void or_lm_stats(long* out, int reset);
 int or_pose_gn(const double* X, const double* uv, int n, const double* K, double* pose, int sum_mode);
+/* The same three with a trace of the data-dependent arms taken (the plain entry points call these without one; tests
+ * assert on the traces that their corpus reaches the arms, tests/test_gpu_pose_degenerate.py).
+ * or_ldlt6_solve_ex trace [OR_LDLT_TRACE]: {the transpositions tr[0..5], final sign (0 zero, 1 positive, 2 negative,
+ * 3 indefinite), the k == 0 exit taken, zero pivots met at k > 0, solve entries set to 0 by the > DBL_MIN test}.
+ * or_pose_lm_ex trace [4][OR_LM_TRACE_ROUND], per round: {active edges, iterations run (-1: no active edge), trials
+ * accepted, trials rejected on rho (LDLT positive, chi2 finite), trials whose LDLT was not positive, trials with a
+ * non-finite chi2 and a positive LDLT, why the trial loop ended (0: ten iterations; bits 1: qmax == 10, 2: rho == 0,
+ * 4: lambda non-finite), the last trial was rejected (classification at an estimate that is not the final one), a
+ * Huber weight was applied in some pass, some pass met a non-finite J entry / weight / error (each tested alone; the
+ * kernel's literal pass), the round repeats the previous one (same active set and Huber state: the kernel's replay), LDLT solves that
+ * left at k == 0, LDLT solves with a zero pivot at k > 0, the LDLT signs seen (bit 1 << sign), solve entries set to 0,
+ * some LDLT solve transposed, where the non-finite edges that have their Huber kernel stood among the kernel's waves (64
+ * consecutive active edges share one Huber decision): bit 1 in a wave without a Huber-weighted edge, 2 in a wave with one, 4 in a wave without
+ * one in a pass in which another wave had one, 8 a robust edge with a NaN chi2 in a wave without one (the kernel
+ * leaves its weight at 1.0 where huber_rho gives NaN)}.
+ * or_pose_gn_ex trace [OR_GN_TRACE]: per iteration i (-1: not run) [i] = 0 continued, 1 stopped on isnan(dx[0]),
+ * 2 stopped on a cost increase, 3 accepted and stopped on |dx| < 1e-6; [10 + i] = the LDLT's sign; [20 + i] = bit 1
+ * its k == 0 exit, bit 2 a zero pivot at k > 0; [30 + i] = -1 no point in the camera plane, else bit 1 a point with
+ * pc_z == 0 off the optical axis (u / 0), bit 2 a point at the camera centre (0 / 0). */
+#define OR_LDLT_TRACE 10
+#define OR_LM_TRACE_ROUND 17
+#define OR_GN_TRACE 40
+int or_ldlt6_solve_ex(const double* H, const double* b, double* x, int variant, int* trace);
+int or_pose_lm_ex(const double* X, const double* uv, int n, const double* K, double* pose, uint8_t* outlier,
+                  int sum_mode, int* trace);
+int or_pose_gn_ex(const double* X, const double* uv, int n, const double* K, double* pose, int sum_mode, int* trace);
 
 /* ---- cv::calcOpticalFlowPyrLK (yavo_oracle_lk.c) ---- */
 /* cv::pyrDown, CV_8U, BORDER_REFLECT_101: dst [(H+1)/2][(W+1)/2]. */

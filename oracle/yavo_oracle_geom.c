@@ -20,8 +20,9 @@
  * tree order of the GPU kernels (sum_mode m >= 1: per-thread strided partial sums over 128 << m threads --
  * 512 for the pose LM (mode 2), 256 for GN (mode 1) -- then a halving tree), so GPU parity can be tested
  * bit-for-bit and the two orders compared within tolerance.
- * sin / cos in SO3::exp use one fixed polynomial kernel (fdlibm's, |x| <= pi/4) on both sides; the
- * reference's std::sin / std::cos may differ by 1 ulp (unpinned).
+ * sin / cos in SO3::exp use one fixed polynomial kernel (fdlibm's, |x| <= pi/4; past it and below 2^20 behind
+ * fdlibm's medium-range argument reduction) on both sides; the reference's std::sin / std::cos may differ by 1 ulp
+ * (unpinned).
  */
 #include "yavo_oracle.h"
 
@@ -440,11 +441,84 @@ void or_cube_batch(const double* t, int n, int flavour, double* out) {
     for (int i = 0; i < n; ++i) out[i] = flavour ? pow(t[i], 3) : or_cube(t[i]);
 }
 
-/* fdlibm __kernel_sin / __kernel_cos (|x| <= pi/4); larger |x|, or the libm flavour, call the C library. */
+/* fdlibm __kernel_sin / __kernel_cos (|x| <= pi/4).  pi/4 < |x| < 2^20: the argument is reduced as fdlibm's
+ * __ieee754_rem_pio2 does in its medium range (Cody-Waite with pi/2 in three 33-bit pieces, always with the cancellation
+ * check) and the kernels take the reduced argument with its tail; the GPU kernels do the same operations
+ * (ya_vo_amd/csrc/yavo_se3.h).  Larger or non-finite |x|, or the libm flavour, call the C library. */
+#define K_TRIG_MAX 1048576.0
+static int dbl_exponent(double x) {
+    uint64_t u;
+    memcpy(&u, &x, sizeof u);
+    return (int)((u >> 52) & 0x7ff);
+}
+
+/* x = n pi/2 + (y[0] + y[1]), |y[0]| <= pi/4 (+ an ulp); returns n mod 4 */
+static int k_rem_pio2(double x, double* y) {
+    const double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00,
+                 pio2_1t = 6.07710050650619224932e-11, pio2_2 = 6.07710050630396597660e-11,
+                 pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21,
+                 pio2_3t = 8.47842766036889956997e-32;
+    const double t0 = fabs(x);
+    const int n = (int)(t0 * invpio2 + 0.5);
+    const double fn = (double)n;
+    double r = t0 - fn * pio2_1, w = fn * pio2_1t;
+    const int j = dbl_exponent(t0);
+    double y0 = r - w;
+    if (j - dbl_exponent(y0) > 16) { /* 2nd iteration, good to 118 bits */
+        double t = r;
+        w = fn * pio2_2;
+        r = t - w;
+        w = fn * pio2_2t - ((t - r) - w);
+        y0 = r - w;
+        if (j - dbl_exponent(y0) > 49) { /* 3rd iteration, 151 bits */
+            t = r;
+            w = fn * pio2_3;
+            r = t - w;
+            w = fn * pio2_3t - ((t - r) - w);
+            y0 = r - w;
+        }
+    }
+    const double y1 = (r - y0) - w;
+    if (x < 0) {
+        y[0] = -y0;
+        y[1] = -y1;
+        return (-n) & 3;
+    }
+    y[0] = y0;
+    y[1] = y1;
+    return n & 3;
+}
+
+static double k_sin_tail(double x, double y) { /* __kernel_sin(x, y, 1) */
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    double z = x * x, v = z * x;
+    double r = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+    return x - ((z * (0.5 * y - v * r) - y) - v * S1);
+}
+
+static double k_cos_tail(double x, double y) { /* __kernel_cos(x, y) */
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    double z = x * x;
+    double r = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+    double hz = 0.5 * z, w = 1.0 - hz;
+    return w + (((1.0 - w) - hz) + (z * r - x * y));
+}
+
 static double k_sin(double x) {
     const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
                  S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
-    if (or_libm_flavour || !(fabs(x) <= 0.78539816339744827900)) return sin(x);
+    if (or_libm_flavour || !(fabs(x) < K_TRIG_MAX)) return sin(x);
+    if (!(fabs(x) <= 0.78539816339744827900)) {
+        double y[2];
+        switch (k_rem_pio2(x, y)) {
+            case 0: return k_sin_tail(y[0], y[1]);
+            case 1: return k_cos_tail(y[0], y[1]);
+            case 2: return -k_sin_tail(y[0], y[1]);
+            default: return -k_cos_tail(y[0], y[1]);
+        }
+    }
     double z = x * x, v = z * x;
     double r = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
     return x + v * (S1 + z * r);
@@ -453,7 +527,16 @@ static double k_sin(double x) {
 static double k_cos(double x) {
     const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
                  C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
-    if (or_libm_flavour || !(fabs(x) <= 0.78539816339744827900)) return cos(x);
+    if (or_libm_flavour || !(fabs(x) < K_TRIG_MAX)) return cos(x);
+    if (!(fabs(x) <= 0.78539816339744827900)) {
+        double y[2];
+        switch (k_rem_pio2(x, y)) {
+            case 0: return k_cos_tail(y[0], y[1]);
+            case 1: return -k_sin_tail(y[0], y[1]);
+            case 2: return -k_cos_tail(y[0], y[1]);
+            default: return k_sin_tail(y[0], y[1]);
+        }
+    }
     double z = x * x;
     double r = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
     double hz = 0.5 * z, w = 1.0 - hz;
@@ -668,9 +751,12 @@ int or_triangulate_matches(const double* Ta, const double* Tb, const double* K, 
 
 /* variant 0 (dynamic MatrixXd, g2o LinearSolverDense): A21 -= A20*temp as a column-wise GEMV
  * (sequential subtraction per term); variant 1 (fixed Matrix6d, test.cc): A21 -= dot(A20 row, temp). */
-static int ldlt6_solve(const double* Hin, const double* b, double* x, int variant) {
+/* trace (optional, OR_LDLT_TRACE ints): {tr[0..5], final sign, the k == 0 exit taken, zero pivots met at k > 0,
+ * solve entries set to 0 by the > DBL_MIN test}. */
+static int ldlt6_solve(const double* Hin, const double* b, double* x, int variant, int* trace) {
     double mat[36];
     int tr[6];
+    int k0_exit = 0, zero_pivots = 0, zeroed = 0;
     memcpy(mat, Hin, sizeof mat); /* row-major; only the lower triangle (i >= j) is read */
     const int n = 6;
     int sign = 0; /* 0 ZeroSign, 1 PositiveSemiDef, 2 NegativeSemiDef, 3 Indefinite */
@@ -714,6 +800,7 @@ static int ldlt6_solve(const double* Hin, const double* b, double* x, int varian
             sign = 0;
             for (int j = 0; j < n; ++j) tr[j] = j;
             ret = 0;
+            k0_exit = 1;
             break;
         }
         if (rs > 0 && valid) {
@@ -723,6 +810,7 @@ static int ldlt6_solve(const double* Hin, const double* b, double* x, int varian
         }
         if (found_zero_pivot && valid) ret = 0;
         else if (!valid) found_zero_pivot = 1;
+        if (!valid) zero_pivots++;
         if (sign == 1) { if (akk < 0) sign = 3; }
         else if (sign == 2) { if (akk > 0) sign = 3; }
         else if (sign == 0) { if (akk > 0) sign = 1; else if (akk < 0) sign = 2; }
@@ -737,13 +825,20 @@ static int ldlt6_solve(const double* Hin, const double* b, double* x, int varian
         for (int i = j + 1; i < n; ++i) v[i] = v[i] - L(i, j) * v[j];
     for (int i = 0; i < n; ++i) {
         if (fabs(L(i, i)) > DBL_MIN) v[i] /= L(i, i);
-        else v[i] = 0;
+        else { v[i] = 0; zeroed++; }
     }
     for (int j = n - 1; j >= 0; --j)
         for (int i = 0; i < j; ++i) v[i] = v[i] - L(j, i) * v[j];
     for (int k = n - 1; k >= 0; --k) { double t = v[k]; v[k] = v[tr[k]]; v[tr[k]] = t; }
 #undef L
     memcpy(x, v, sizeof v);
+    if (trace) {
+        for (int k = 0; k < n; ++k) trace[k] = tr[k];
+        trace[6] = sign;
+        trace[7] = k0_exit;
+        trace[8] = zero_pivots;
+        trace[9] = zeroed;
+    }
     return positive;
 }
 
@@ -916,15 +1011,56 @@ void or_lm_stats(long* out, int reset) {
     }
 }
 
+/* The per-round trace of or_pose_lm_ex (OR_LM_TRACE_ROUND ints a round, yavo_oracle.h). */
+enum { LT_ACTIVE, LT_ITERS, LT_ACCEPTED, LT_REJECTED, LT_NOT_POSITIVE, LT_CHI_NONFINITE, LT_END, LT_LAST_REJECTED,
+       LT_HUBER, LT_LITERAL, LT_REPLAY, LT_LDLT_K0, LT_LDLT_ZERO_PIVOT, LT_LDLT_SIGNS, LT_LDLT_ZEROED, LT_LDLT_PIVOTED,
+       LT_LITERAL_WAVES };
+
+/* What the GPU kernel's pass over the active edges at T decides from its operands (tracing only; the errors are the
+ * ones compute_active_errors left): a Huber weight applied (a robust edge past delta^2), and a non-finite J entry,
+ * weight or error, each operand tested alone (the kernel then redoes the pass in the literal J^T Omega J form; it
+ * tests a sum of the operands, which may also overflow on finite ones: the literal form gives the same bits there).
+ * LT_LITERAL_WAVES places the non-finite edge: the kernel evaluates Huber for the 64 consecutive active edges of one
+ * wave's iteration only when one of them is past delta^2, whatever the workgroup's width. */
+static void trace_pass(const lm_problem* P, const double* T, int* tr) {
+    int pass_huber = 0, quiet_bad = 0;
+    for (int a0 = 0; a0 < P->n_active; a0 += 64) {
+        int wave_huber = 0, any_bad = 0, bad = 0, bad_nan_c2 = 0; /* bad: on an edge that has its Huber kernel */
+        for (int a = a0; a < P->n_active && a < a0 + 64; ++a) {
+            int i = P->active[a];
+            const double* e = P->err + 2 * i;
+            double J[12], w = 1.0;
+            edge_jacobian(T, P->K, P->X + 3 * i, J);
+            if (P->robust[i]) {
+                huber_rho(edge_chi2(e), &w);
+                if (edge_chi2(e) > 1.0) wave_huber = 1;
+            }
+            int fin = isfinite(w) && isfinite(e[0]) && isfinite(e[1]);
+            for (int k = 0; k < 12; ++k) fin = fin && isfinite(J[k]);
+            if (!fin) any_bad = 1;
+            if (!fin && P->robust[i]) bad = 1;
+            if (P->robust[i] && isnan(edge_chi2(e))) bad_nan_c2 = 1;
+        }
+        if (wave_huber) tr[LT_HUBER] = 1;
+        if (any_bad) tr[LT_LITERAL] = 1;
+        if (bad) tr[LT_LITERAL_WAVES] |= wave_huber ? 2 : 1;
+        if (bad_nan_c2 && !wave_huber) tr[LT_LITERAL_WAVES] |= 8;
+        pass_huber |= wave_huber;
+        quiet_bad |= bad && !wave_huber;
+    }
+    if (quiet_bad && pass_huber) tr[LT_LITERAL_WAVES] |= 4;
+}
+
 /* SparseOptimizer::optimize(iterations) with OptimizationAlgorithmLevenberg::solve per iteration.
- * Returns the number of iterations run (-1 when there is no active edge). */
-static int lm_optimize(lm_problem* P, double* T, int iterations) {
+ * Returns the number of iterations run (-1 when there is no active edge).  tr (optional): this round's trace. */
+static int lm_optimize(lm_problem* P, double* T, int iterations, int* tr) {
     if (P->n_active == 0) return -1;
     double lambda = 0, ni = 2;
     const double tau = 1e-5, goodLower = 1.0 / 3.0, goodUpper = 2.0 / 3.0;
     int it;
     for (it = 0; it < iterations; ++it) {
         compute_active_errors(P, T);
+        if (tr) trace_pass(P, T, tr);
         double currentChi = active_robust_chi2(P);
         double H[36], b[6];
         build_system(P, T, H, b);
@@ -944,14 +1080,25 @@ static int lm_optimize(lm_problem* P, double* T, int iterations) {
             double Hl[36], x[6];
             memcpy(Hl, H, sizeof Hl);
             for (int j = 0; j < 6; ++j) Hl[j * 7] += lambda;
-            int ok2 = ldlt6_solve(Hl, b, x, 0);
+            int lt[OR_LDLT_TRACE];
+            int ok2 = ldlt6_solve(Hl, b, x, 0, lt);
+            if (tr) {
+                tr[LT_LDLT_K0] += lt[7];
+                tr[LT_LDLT_ZERO_PIVOT] += lt[8] > 0;
+                tr[LT_LDLT_SIGNS] |= 1 << lt[6];
+                tr[LT_LDLT_ZEROED] += lt[9];
+                for (int j = 0; j < 6; ++j) tr[LT_LDLT_PIVOTED] |= lt[j] != j;
+            }
             double Tn[7];
             or_se3_exp(x, Tn); /* VertexPose::oplusImpl: exp(update) * estimate */
             double Tnew[7];
             or_se3_mul(Tn, T, Tnew);
             memcpy(T, Tnew, sizeof Tnew);
             compute_active_errors(P, T);
+            if (tr) trace_pass(P, T, tr);
             tempChi = active_robust_chi2(P);
+            if (tr && !ok2) tr[LT_NOT_POSITIVE]++;
+            if (tr && ok2 && !isfinite(tempChi)) tr[LT_CHI_NONFINITE]++;
             if (!ok2) tempChi = DBL_MAX;
             rho = currentChi - tempChi;
             double scale = 1;
@@ -964,6 +1111,7 @@ static int lm_optimize(lm_problem* P, double* T, int iterations) {
             g_lm_stats[1]++;
             if (rho > 0 && isfinite(tempChi) && ok2) {
                 g_lm_stats[2]++;
+                if (tr) { tr[LT_ACCEPTED]++; tr[LT_LAST_REJECTED] = 0; }
                 double t = 2 * rho - 1;
                 double alpha = 1. - or_lm_cube(t);
                 alpha = alpha < goodUpper ? alpha : goodUpper;
@@ -975,11 +1123,16 @@ static int lm_optimize(lm_problem* P, double* T, int iterations) {
                 lambda *= ni;
                 ni *= 2;
                 memcpy(T, Tbak, sizeof Tbak); /* pop */
+                if (tr) {
+                    if (ok2 && isfinite(tempChi)) tr[LT_REJECTED]++;
+                    tr[LT_LAST_REJECTED] = 1;
+                }
                 if (!isfinite(lambda)) break;
             }
             qmax++;
         } while (rho < 0 && qmax < 10);
         if (qmax == 10 || rho == 0 || !isfinite(lambda)) {
+            if (tr) tr[LT_END] = (qmax == 10 ? 1 : 0) | (rho == 0 ? 2 : 0) | (!isfinite(lambda) ? 4 : 0);
             it++;
             break; /* Terminate */
         }
@@ -990,8 +1143,8 @@ static int lm_optimize(lm_problem* P, double* T, int iterations) {
 /* LoopHandler::optimizePoseOnly, src/LoopHandler.cc:730-861.  X [n][3] world points, uv [n][2] measurements
  * (kp.x = row, kp.y = col), K row-major 3x3, pose in/out (SE3d::data()).  outlier[n] = final flags.
  * Returns the inlier count (n - outliers). */
-int or_pose_lm(const double* X, const double* uv, int n, const double* K, double* pose, uint8_t* outlier,
-               int sum_mode) {
+int or_pose_lm_ex(const double* X, const double* uv, int n, const double* K, double* pose, uint8_t* outlier,
+                  int sum_mode, int* trace) {
     uint8_t* level = (uint8_t*)calloc((size_t)n + 1, 1);
     uint8_t* robust = (uint8_t*)malloc((size_t)n + 1);
     int* active = (int*)malloc(sizeof(int) * ((size_t)n + 1));
@@ -1001,17 +1154,28 @@ int or_pose_lm(const double* X, const double* uv, int n, const double* K, double
     const double chi2th = 5.991;
     double prior[7], T[7];
     memcpy(prior, pose, sizeof prior);
-    int outlierCount = 0;
+    int outlierCount = 0, changed = 0;
     for (int round = 0; round < 4; ++round) {
         memcpy(T, prior, sizeof T); /* vertexPose->setEstimate(currentFrame->pose) */
         int na = 0;
         for (int i = 0; i < n; ++i)
             if (level[i] == 0) active[na++] = i; /* initializeOptimization(): level-0 edges */
         lm_problem P = {na, active, X, uv, K, robust, err, sum_mode};
-        lm_optimize(&P, T, 10);
+        int* tr = trace ? trace + OR_LM_TRACE_ROUND * round : NULL;
+        if (tr) {
+            memset(tr, 0, sizeof(int) * OR_LM_TRACE_ROUND);
+            tr[LT_ACTIVE] = na;
+            /* the round repeats the last one operation for operation: the last classification moved no edge between
+             * levels and, across the Huber drop after round 2, that round applied no Huber weight */
+            tr[LT_REPLAY] = round > 0 && !changed && (round != 3 || !tr[LT_HUBER - OR_LM_TRACE_ROUND]);
+        }
+        const int its = lm_optimize(&P, T, 10, tr);
+        if (tr) tr[LT_ITERS] = its;
         outlierCount = 0;
+        changed = 0;
         for (int i = 0; i < n; ++i) {
             if (outlier[i]) edge_error(T, K, X + 3 * i, uv + 2 * i, err + 2 * i); /* e->computeError() */
+            const uint8_t lev = level[i];
             if (edge_chi2(err + 2 * i) > chi2th) {
                 outlier[i] = 1;
                 level[i] = 1;
@@ -1020,6 +1184,7 @@ int or_pose_lm(const double* X, const double* uv, int n, const double* K, double
                 outlier[i] = 0;
                 level[i] = 0;
             }
+            changed |= lev != level[i];
             if (round == 2) robust[i] = 0; /* e->setRobustKernel(nullptr) */
         }
     }
@@ -1028,10 +1193,17 @@ int or_pose_lm(const double* X, const double* uv, int n, const double* K, double
     return n - outlierCount;
 }
 
+int or_pose_lm(const double* X, const double* uv, int n, const double* K, double* pose, uint8_t* outlier,
+               int sum_mode) {
+    return or_pose_lm_ex(X, uv, n, K, pose, outlier, sum_mode, NULL);
+}
+
 /* bundleAdjustmentGaussNewton, src/test.cc:172-244 (cx, cy in the projection; 10 iterations; stop on cost
  * increase or |dx| < 1e-6; NaN guard). Returns iterations accepted. */
-int or_pose_gn(const double* X, const double* uv, int n, const double* K, double* pose, int sum_mode) {
+int or_pose_gn_ex(const double* X, const double* uv, int n, const double* K, double* pose, int sum_mode, int* trace) {
     const int iterations = 10;
+    if (trace)
+        for (int i = 0; i < OR_GN_TRACE; ++i) trace[i] = -1;
     double cost = 0, lastCost = 0;
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     int acc = 0;
@@ -1045,6 +1217,10 @@ int or_pose_gn(const double* X, const double* uv, int n, const double* K, double
         for (int i = 0; i < n; i++) {
             double pc[3];
             or_se3_act(pose, X + 3 * i, pc);
+            if (trace && pc[2] == 0) {
+                if (trace[30 + iter] < 0) trace[30 + iter] = 0;
+                trace[30 + iter] |= pc[0] == 0 && pc[1] == 0 ? 2 : 1;
+            }
             double inv_z = 1.0 / pc[2];
             double inv_z2 = inv_z * inv_z;
             double proj0 = fx * pc[0] / pc[2] + cx, proj1 = fy * pc[1] / pc[2] + cy;
@@ -1064,7 +1240,13 @@ int or_pose_gn(const double* X, const double* uv, int n, const double* K, double
         double H[36], b[6], dx[6];
         for (int i = 0; i < 36; ++i) H[i] = sum_total(&sH[i]);
         for (int i = 0; i < 6; ++i) b[i] = sum_total(&sb[i]);
-        ldlt6_solve(H, b, dx, 1);
+        int lt[OR_LDLT_TRACE];
+        ldlt6_solve(H, b, dx, 1, lt);
+        if (trace) {
+            trace[iter] = isnan(dx[0]) ? 1 : (iter > 0 && cost >= lastCost) ? 2 : 0;
+            trace[10 + iter] = lt[6];
+            trace[20 + iter] = lt[7] | (lt[8] > 0 ? 2 : 0);
+        }
         if (isnan(dx[0])) break;
         if (iter > 0 && cost >= lastCost) break;
         double Tn[7], Tnew[7];
@@ -1077,13 +1259,23 @@ int or_pose_gn(const double* X, const double* uv, int n, const double* K, double
         double q0 = dx[0] * dx[0] + (dx[2] * dx[2] + dx[4] * dx[4]);
         double q1 = dx[1] * dx[1] + (dx[3] * dx[3] + dx[5] * dx[5]);
         double nrm = sqrt(q0 + q1);
-        if (nrm < 1e-6) break;
+        if (nrm < 1e-6) {
+            if (trace) trace[iter] = 3;
+            break;
+        }
 #undef sc
     }
     free(sums);
     return acc;
 }
 
+int or_pose_gn(const double* X, const double* uv, int n, const double* K, double* pose, int sum_mode) {
+    return or_pose_gn_ex(X, uv, n, K, pose, sum_mode, NULL);
+}
+
 /* exported helpers for tests */
-int or_ldlt6_solve(const double* H, const double* b, double* x, int variant) { return ldlt6_solve(H, b, x, variant); }
+int or_ldlt6_solve(const double* H, const double* b, double* x, int variant) { return ldlt6_solve(H, b, x, variant, NULL); }
+int or_ldlt6_solve_ex(const double* H, const double* b, double* x, int variant, int* trace) {
+    return ldlt6_solve(H, b, x, variant, trace);
+}
 void or_cv_svd(const double* src, int n, double* w, double* u, double* vt) { cv_svd_square(src, n, w, u, vt); }

@@ -66,6 +66,9 @@ class Oracle:
             "or_ldlt6_solve": (_I, [_P, _P, _P, _I]),
             "or_pose_lm": (_I, [_P, _P, _I, _P, _P, _P, _I]),
             "or_pose_gn": (_I, [_P, _P, _I, _P, _P, _I]),
+            "or_ldlt6_solve_ex": (_I, [_P, _P, _P, _I, _P]),
+            "or_pose_lm_ex": (_I, [_P, _P, _I, _P, _P, _P, _I, _P]),
+            "or_pose_gn_ex": (_I, [_P, _P, _I, _P, _P, _I, _P]),
             "or_lm_stats": (None, [_P, _I]),
             "or_pyr_down": (None, [_P, _I, _I, _I, _P]),
             "or_scharr": (None, [_P, _I, _I, _I, _P]),
@@ -345,6 +348,44 @@ class Oracle:
         T = np.array(pose, np.float64).copy()
         it = self.lib.or_pose_gn(_p(X), _p(uv), len(X), _p(K), _p(T), sum_mode)
         return T, it
+
+    LM_TRACE_FIELDS = ("active", "iters", "accepted", "rejected", "not_positive", "chi_nonfinite", "end",
+                       "last_rejected", "huber", "literal", "replay", "ldlt_k0", "ldlt_zero_pivot", "ldlt_signs",
+                       "ldlt_zeroed", "ldlt_pivoted", "literal_waves")
+
+    def ldlt6_ex(self, H, b, variant=0):
+        """-> (positive, x, trace dict: tr (the six transpositions), sign, k0_exit, zero_pivots (at k > 0), zeroed (solve
+        entries the > DBL_MIN test set to 0))."""
+        H = np.ascontiguousarray(H, np.float64).reshape(36)
+        b = np.ascontiguousarray(b, np.float64)
+        x = np.zeros(6)
+        tr = np.zeros(10, np.int32)
+        pos = self.lib.or_ldlt6_solve_ex(_p(H), _p(b), _p(x), variant, _p(tr))
+        return bool(pos), x, dict(tr=tuple(int(v) for v in tr[:6]), sign=int(tr[6]), k0_exit=int(tr[7]),
+                                  zero_pivots=int(tr[8]), zeroed=int(tr[9]))
+
+    def pose_lm_ex(self, X, uv, K, pose, sum_mode=0):
+        """-> (pose, outlier flags, inliers, one trace dict per round with LM_TRACE_FIELDS; oracle/yavo_oracle.h)."""
+        X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        T = np.array(pose, np.float64).copy()
+        out = np.zeros(max(len(X), 1), np.uint8)
+        tr = np.zeros((4, len(self.LM_TRACE_FIELDS)), np.int32)
+        inl = self.lib.or_pose_lm_ex(_p(X), _p(uv), len(X), _p(K), _p(T), _p(out), sum_mode, _p(tr))
+        return T, out[:len(X)].astype(bool), inl, [dict(zip(self.LM_TRACE_FIELDS, map(int, r))) for r in tr]
+
+    def pose_gn_ex(self, X, uv, K, pose, sum_mode=0):
+        """-> (pose, accepted iterations, trace dict: stop [10] (-1 not run, 0 continued, 1 isnan(dx[0]), 2 cost increase,
+        3 |dx| < 1e-6), sign [10], ldlt [10] (bit 1: k == 0 exit, bit 2: zero pivot at k > 0), plane [10] (-1 no point
+        with pc_z == 0, else bit 1: one off the optical axis, bit 2: one at the camera centre))."""
+        X = np.ascontiguousarray(X, np.float64).reshape(-1, 3)
+        uv = np.ascontiguousarray(uv, np.float64).reshape(-1, 2)
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        T = np.array(pose, np.float64).copy()
+        tr = np.zeros(40, np.int32)
+        it = self.lib.or_pose_gn_ex(_p(X), _p(uv), len(X), _p(K), _p(T), sum_mode, _p(tr))
+        return T, it, dict(stop=tr[:10].tolist(), sign=tr[10:20].tolist(), ldlt=tr[20:30].tolist(), plane=tr[30:].tolist())
 
     # ---- cv::calcOpticalFlowPyrLK (SURVEY.md 8f row 1) ----
     def pyr_down(self, img):

@@ -237,7 +237,7 @@ int join_build(yv_batch* b, hipStream_t s) {
 
 bool finite_pose(const double* p) {
     for (int i = 0; i < 7; ++i)
-        if (!(p[i] == p[i])) return false;
+        if (!std::isfinite(p[i])) return false;  // NaN or +-inf
     return true;
 }
 
@@ -2448,6 +2448,21 @@ int yv_debug_ess_models(yv_essential* es, const double* d_q1, const double* d_q2
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : es->ctx->stream;
     const int rc = yavo::launch_debug_ess_models(es->P, d_q1, d_q2, n_sets, d_models, d_nmod, s);
     if (rc != 0) return rc == -1 ? YV_ERR_INVALID : YV_ERR_HIP;
+    return check_launch();
+}
+
+// Test entry point (tests/test_gpu_pose_degenerate.py; like yv_debug_xlane not part of the public headers): the batch's
+// track LM alone (launch_track_pose: the fixed-stride layout, track t owns d_counts[t] edges from t * stride) on device
+// buffers; d_priors [n][7] is read, d_poses [n][7] written.
+int yv_debug_track_pose(yv_ctx* ctx, int n_tracks, const int32_t* d_counts, int stride, const double* d_X,
+                        const double* d_uv, const double* d_K, const double* d_priors, double* d_poses,
+                        uint8_t* d_outlier, int32_t* d_inliers, void* stream) {
+    if (!ctx || n_tracks <= 0 || stride < 0 || !d_counts || !d_X || !d_uv || !d_K || !d_priors || !d_poses ||
+        !d_outlier || !d_inliers)
+        return YV_ERR_INVALID;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+    yavo::launch_track_pose(n_tracks, d_counts, stride, d_X, d_uv, d_K, d_priors, d_poses, d_outlier, d_inliers, s);
     return check_launch();
 }
 

@@ -1812,6 +1812,103 @@ extern "C" int yv_pose_lm_sum_mode(int n_problems) {
                                                                                : yavo::geom::kLMThreads);
 }
 
+// ------------------------------------------------------------------------------------------------
+// test entry point (tests/test_gpu_pose_degenerate.py; like yv_debug_xlane not part of the public headers)
+// ------------------------------------------------------------------------------------------------
+// The two LDLT forms the pose kernels instantiate, alone, one system a lane: form 0 = ldlt6_solve_lds<0> on (H, lambda)
+// with H, b and x in LDS as the LM holds them; form 1 = ldlt6_solve<1> on H with lambda added on the diagonal (the
+// GN's private arrays).  x [n][6], positive [n].
+namespace yavo {
+namespace geom {
+template <int FORM>
+__global__ __launch_bounds__(64) void debug_ldlt6_kernel(const double* __restrict__ H, const double* __restrict__ lam,
+                                                         const double* __restrict__ b, int n, double* __restrict__ x,
+                                                         int32_t* __restrict__ positive) {
+    const int lane = threadIdx.x;
+    const int k = blockIdx.x * 64 + lane;
+    if (k >= n) return;  // no barrier below: every lane works on LDS words of its own
+    if constexpr (FORM == 0) {
+        __shared__ double s_H[64][36], s_b[64][6], s_x[64][6];
+        for (int i = 0; i < 36; ++i) s_H[lane][i] = H[36 * (int64_t)k + i];
+        for (int i = 0; i < 6; ++i) s_b[lane][i] = b[6 * (int64_t)k + i];
+        const bool pos = ldlt6_solve_lds<0>(s_H[lane], lam[k], s_b[lane], s_x[lane]);
+        for (int i = 0; i < 6; ++i) x[6 * (int64_t)k + i] = s_x[lane][i];
+        positive[k] = pos ? 1 : 0;
+    } else {
+        double Hd[36], bd[6], xd[6];
+        for (int i = 0; i < 36; ++i) Hd[i] = H[36 * (int64_t)k + i];
+        for (int i = 0; i < 6; ++i) Hd[i * 7] = Hd[i * 7] + lam[k];
+        for (int i = 0; i < 6; ++i) bd[i] = b[6 * (int64_t)k + i];
+        const bool pos = ldlt6_solve<1>(Hd, bd, xd);
+        for (int i = 0; i < 6; ++i) x[6 * (int64_t)k + i] = xd[i];
+        positive[k] = pos ? 1 : 0;
+    }
+}
+
+// SE3::exp's sin / cos (yavo_se3.h: the polynomial range, the shared reduction past pi/4, the library past 2^20)
+__global__ __launch_bounds__(64) void debug_sincos_kernel(const double* __restrict__ x, int n, double* __restrict__ s,
+                                                          double* __restrict__ c) {
+    const int k = blockIdx.x * 64 + threadIdx.x;
+    if (k >= n) return;
+    s[k] = k_sin(x[k]);
+    c[k] = k_cos(x[k]);
+}
+}  // namespace geom
+}  // namespace yavo
+
+// x [n] -> s [n], c [n]: host arrays
+extern "C" int yv_debug_sincos(const double* x, int n, double* s, double* c) {
+    if (!x || !s || !c || n < 0) return -1;
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    double* d = nullptr;
+    if (hipMalloc(&d, 3 * N * sizeof(double)) != hipSuccess) return -2;
+    bool ok = hipMemcpy(d, x, N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        hipLaunchKernelGGL(yavo::geom::debug_sincos_kernel, dim3((n + 63) / 64), dim3(64), 0, nullptr, d, n, d + N,
+                           d + 2 * N);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(s, d + N, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(c, d + 2 * N, N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(d);
+    return ok ? 0 : -2;
+}
+
+// H [n][36] row-major symmetric, lambda [n], b [n][6], x [n][6], positive [n]: host arrays
+extern "C" int yv_debug_ldlt6(int form, const double* H, const double* lambda, const double* b, int n, double* x,
+                              int32_t* positive) {
+    if ((form != 0 && form != 1) || !H || !lambda || !b || !x || !positive || n < 0) return -1;
+    if (n == 0) return 0;
+    const size_t N = (size_t)n;
+    const size_t nd = N * (36 + 1 + 6 + 6);
+    double* d = nullptr;
+    int32_t* dp = nullptr;
+    if (hipMalloc(&d, nd * sizeof(double)) != hipSuccess) return -2;
+    if (hipMalloc(&dp, N * sizeof(int32_t)) != hipSuccess) {
+        (void)hipFree(d);
+        return -2;
+    }
+    double *dH = d, *dl = dH + 36 * N, *db = dl + N, *dx = db + 6 * N;
+    bool ok = hipMemcpy(dH, H, 36 * N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(dl, lambda, N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(db, b, 6 * N * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        if (form == 0)
+            hipLaunchKernelGGL(yavo::geom::debug_ldlt6_kernel<0>, dim3((n + 63) / 64), dim3(64), 0, nullptr, dH, dl, db, n,
+                               dx, dp);
+        else
+            hipLaunchKernelGGL(yavo::geom::debug_ldlt6_kernel<1>, dim3((n + 63) / 64), dim3(64), 0, nullptr, dH, dl, db, n,
+                               dx, dp);
+        ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+             hipMemcpy(x, dx, 6 * N * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+             hipMemcpy(positive, dp, N * sizeof(int32_t), hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(d);
+    (void)hipFree(dp);
+    return ok ? 0 : -2;
+}
+
 #ifdef YAVO_LM_PROFILE
 // profiling builds only (lib/libyavo_prof.so): per-workgroup pose-LM phase cycle counts of the last launch
 extern "C" int yv_debug_lm_prof(unsigned long long* out) {

@@ -19,10 +19,74 @@ __device__ __forceinline__ void mm3(const double* A, const double* B, double* C)
     for (int i = 0; i < 9; ++i) C[i] = R[i];
 }
 
-// the library's full-range sin / cos (Payne-Hanek reduction and all): rare (|x| > pi/4), and register-hungry, so kept
-// out of line -- inlined into the pose LM's lane-0 step they set the whole kernel's register peak
-__device__ __noinline__ double k_sin_full(double x) { return sin(x); }
-__device__ __noinline__ double k_cos_full(double x) { return cos(x); }
+// sin / cos past pi/4, operation for operation the oracle's (k_rem_pio2 / k_sin_tail / k_cos_tail in
+// oracle/yavo_oracle_geom.c): below 2^20 fdlibm's medium-range reduction (Cody-Waite with pi/2 in three 33-bit pieces,
+// always with the cancellation check) and its kernels on the reduced argument with its tail; the device library's and
+// the host's own sin / cos differ by an ulp there.  Larger or non-finite arguments go to the library (Payne-Hanek
+// reduction and all).  Rare and register-hungry, so kept out of line -- inlined into the pose LM's lane-0 step they
+// set the whole kernel's register peak.
+__device__ __forceinline__ int dbl_exponent(double x) { return (__double2hiint(x) >> 20) & 0x7ff; }
+
+// x = n pi/2 + (y0 + y1), |y0| <= pi/4 (+ an ulp); returns n mod 4
+__device__ __forceinline__ int k_rem_pio2(double x, double& y0o, double& y1o) {
+    const double invpio2 = 6.36619772367581382433e-01, pio2_1 = 1.57079632673412561417e+00,
+                 pio2_1t = 6.07710050650619224932e-11, pio2_2 = 6.07710050630396597660e-11,
+                 pio2_2t = 2.02226624879595063154e-21, pio2_3 = 2.02226624871116645580e-21,
+                 pio2_3t = 8.47842766036889956997e-32;
+    const double t0 = fabs(x);
+    const int n = (int)(t0 * invpio2 + 0.5);
+    const double fn = (double)n;
+    double r = t0 - fn * pio2_1, w = fn * pio2_1t;
+    const int j = dbl_exponent(t0);
+    double y0 = r - w;
+    if (j - dbl_exponent(y0) > 16) {  // 2nd iteration, good to 118 bits
+        double t = r;
+        w = fn * pio2_2;
+        r = t - w;
+        w = fn * pio2_2t - ((t - r) - w);
+        y0 = r - w;
+        if (j - dbl_exponent(y0) > 49) {  // 3rd iteration, 151 bits
+            t = r;
+            w = fn * pio2_3;
+            r = t - w;
+            w = fn * pio2_3t - ((t - r) - w);
+            y0 = r - w;
+        }
+    }
+    const double y1 = (r - y0) - w;
+    const bool neg = x < 0;
+    y0o = neg ? -y0 : y0;
+    y1o = neg ? -y1 : y1;
+    return (neg ? -n : n) & 3;
+}
+
+__device__ __forceinline__ double k_sin_tail(double x, double y) {  // __kernel_sin(x, y, 1)
+    const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
+                 S4 = 2.75573137070700676789e-06, S5 = -2.50507602534068634195e-08, S6 = 1.58969099521155010221e-10;
+    double z = x * x, v = z * x;
+    double r = S2 + z * (S3 + z * (S4 + z * (S5 + z * S6)));
+    return x - ((z * (0.5 * y - v * r) - y) - v * S1);
+}
+
+__device__ __forceinline__ double k_cos_tail(double x, double y) {  // __kernel_cos(x, y)
+    const double C1 = 4.16666666666666019037e-02, C2 = -1.38888888888741095749e-03, C3 = 2.48015872894767294178e-05,
+                 C4 = -2.75573143513906633035e-07, C5 = 2.08757232129817482790e-09, C6 = -1.13596475577881948265e-11;
+    double z = x * x;
+    double r = z * (C1 + z * (C2 + z * (C3 + z * (C4 + z * (C5 + z * C6)))));
+    double hz = 0.5 * z, w = 1.0 - hz;
+    return w + (((1.0 - w) - hz) + (z * r - x * y));
+}
+
+// q = 0: sin(x), q = 1: cos(x) = sin(x + pi/2)
+__device__ __noinline__ double k_trig_full(double x, int q) {
+    if (!(fabs(x) < 1048576.0)) return q ? cos(x) : sin(x);
+    double y0, y1;
+    const int n = (k_rem_pio2(x, y0, y1) + q) & 3;
+    const double v = (n & 1) ? k_cos_tail(y0, y1) : k_sin_tail(y0, y1);
+    return (n & 2) ? -v : v;
+}
+__device__ __forceinline__ double k_sin_full(double x) { return k_trig_full(x, 0); }
+__device__ __forceinline__ double k_cos_full(double x) { return k_trig_full(x, 1); }
 
 __device__ __forceinline__ double k_sin(double x) {
     const double S1 = -1.66666666666666324348e-01, S2 = 8.33333333332248946124e-03, S3 = -1.98412698298579493134e-04,
