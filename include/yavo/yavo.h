@@ -163,6 +163,30 @@ int yv_set_keypoint_select(yv_ctx* ctx, int nms_radius, int cell_rows, int cell_
 int yv_select_corners(yv_ctx* ctx, int H, int W, const int32_t* rc, const float* resp, int n, int max_kp,
                       int32_t* out_rc, float* out_resp, int* n_out);
 
+/* ---- rotation-steered BRIEF from the intensity centroid (beyond the reference; exact, all integer) ---- */
+/* With b the blurred image the descriptor samples and S(r, c) = b[clamp(r, 0, H - 1)][clamp(c, 0, W - 1)] (under
+ * steering every read is clamped: no column W, no row H, no wrap), a keypoint at (row, col) has the moments
+ *   m10 = sum dc * S(row + dr, col + dc),  m01 = sum dr * S(row + dr, col + dc)  over the disc dr^2 + dc^2 <= radius^2,
+ * the bin = the smallest k that maximises m10 * dirs[k][0] + m01 * dirs[k][1] (a flat patch: bin 0), and test t
+ * compares S(row + o[0], col + o[1]) > S(row + o[2], col + o[3]) with o = offsets[bin][t]; bit t is bit t % 8 of
+ * featVec[t / 8] as before, and the record is otherwise unchanged.  The keypoint set (checkBoundry, the cut, kp_count,
+ * the order, id) does not change.  n_bins = 0 (the default) switches steering off, radius and the tables are then
+ * ignored and yv_describe / yv_batch_run launch exactly the unsteered descriptor; n_bins in 1..64 switches it on with
+ * radius in 1..15, |dirs| <= 256 and |offsets| <= 15 in every component (every score then fits in int32).  The tables
+ * are copied at the call; the setting lives on the context: yv_describe and every yv_batch_run of the context's
+ * batches follow it from the next call on (ya_vo_amd/steering.py builds the default tables: the offsets table rotated
+ * to n_bins directions).  YV_ERR_INVALID for n_bins outside 0..64 and, with n_bins > 0, a NULL table, a radius outside
+ * 1..15 or a component out of range, all checked before the context; then for a NULL context. */
+int yv_set_brief_steering(yv_ctx* ctx, int n_bins, int radius, const int16_t* dirs /* [n_bins][2] = (dcol, drow) */,
+                          const int8_t* offsets /* [n_bins][256][4] = {drow1, dcol1, drow2, dcol2} */);
+/* Moments (m10, m01) and bin of n positions rc[2 * i ..] = (row, col), anywhere inside the H x W image, under the
+ * context's steering: blurs as yv_describe does, applies no boundary filter.  yv_describe's records carry id = the
+ * input index, so bin[id] belongs to a record of the same list.  Checked before the context: YV_ERR_INVALID for a
+ * NULL img, rc, moments or bin with n > 0, n < 0, H < 9, W < 9, stride < W or a position outside the image;
+ * YV_ERR_CAPACITY for n > 4096; then YV_ERR_INVALID for a NULL context or with steering off. */
+int yv_orient(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const int32_t* rc, int n,
+              int32_t* moments /* [n][2] = (m10, m01) */, uint8_t* bin /* [n] */);
+
 /* ---- batched device pipeline (inputs resident in HBM) ---------------------------------------------- */
 /* A batch owns device workspace for up to max_images images of H x W and max_pairs match pairs.  Slot
  * index max_images is the "carry" slot: it holds the keypoints / descriptors of one image of the
@@ -196,6 +220,14 @@ typedef struct yv_batch_match2_view {
 /* Device views of the filter's arrays (the last run with a filter on); YV_ERR_INVALID before the filter was ever
  * switched on. */
 int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v);
+typedef struct yv_batch_orient_view {
+    const uint8_t* bin;               /* [max_images + 1][max_kp], keypoint order */
+    const int32_t* moments;           /* [max_images + 1][max_kp][2] = (m10, m01) */
+} yv_batch_orient_view;
+/* Device views of the orientation of every keypoint of the last run with steering on (yv_set_brief_steering), the
+ * carry slot's rows copied with its keypoints.  The two arrays are allocated by the first run with steering on:
+ * YV_ERR_INVALID before it. */
+int yv_batch_orient_view_get(yv_batch* b, yv_batch_orient_view* v);
 /* The gates of the following runs, one per pair of yv_batch_set_pairs (gates[4 * p ..] as in yv_match_gated); gates
  * == NULL or n_pairs == 0 switches gating off (the default).  With gates set, yv_batch_run replaces its matcher
  * launches (forward, top-2 and swapped pairs alike) by the gated matcher; removeOutliers, the match filter, the

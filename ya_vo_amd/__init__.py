@@ -63,6 +63,10 @@ class _BatchMatch2View(ctypes.Structure):
     _fields_ = [("nn2", ctypes.c_void_p), ("rev", ctypes.c_void_p), ("keep", ctypes.c_void_p)]
 
 
+class _BatchOrientView(ctypes.Structure):
+    _fields_ = [("bin", ctypes.c_void_p), ("moments", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # symbol -> (restype, argtypes); the same list the C header declares (tests check they all resolve)
@@ -99,6 +103,9 @@ SIGNATURES = {
     "yv_batch_set_match_gates": (_I, [_P, _P, _I]),
     "yv_set_keypoint_select": (_I, [_P, _I, _I, _I, _I]),
     "yv_select_corners": (_I, [_P, _I, _I, _P, _P, _I, _I, _P, _P, ctypes.POINTER(_I)]),
+    "yv_set_brief_steering": (_I, [_P, _I, _I, _P, _P]),
+    "yv_orient": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    "yv_batch_orient_view_get": (_I, [_P, ctypes.POINTER(_BatchOrientView)]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -478,6 +485,35 @@ class Context(_GeomMixin):
         o = np.ascontiguousarray(offsets, dtype=np.int8).reshape(256, 4)
         _check(self.lib.yv_set_brief_offsets(self.handle, _ptr(o)), "yv_set_brief_offsets")
 
+    def set_brief_steering(self, tables=None, radius: int = 15) -> None:
+        """Rotation-steered descriptors (yv_set_brief_steering): tables = (dirs [n_bins, 2] (dcol, drow), offsets
+        [n_bins, 256, 4]), e.g. ya_vo_amd.steering.steering_tables(offsets), with the moments over the disc of `radius`
+        pixels; None (the default) switches steering off.  describe and every run of this context's batches follow
+        it."""
+        if tables is None:
+            _check(self.lib.yv_set_brief_steering(self.handle, 0, 0, None, None), "yv_set_brief_steering")
+            return
+        dirs = np.ascontiguousarray(tables[0], dtype=np.int16).reshape(-1, 2)
+        off = np.ascontiguousarray(tables[1], dtype=np.int8).reshape(-1, 256, 4)
+        if len(dirs) != len(off) or len(dirs) == 0:
+            raise ValueError("dirs and offsets must hold the same number of bins, at least one")
+        _check(self.lib.yv_set_brief_steering(self.handle, len(dirs), int(radius), _ptr(dirs), _ptr(off)),
+               "yv_set_brief_steering")
+
+    def orient(self, img: np.ndarray, rc: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """yv_orient: the centroid moments and the bin of positions rc [n, 2] (row, col) anywhere inside img, under
+        the context's steering -> (moments [n, 2] int32 (m10, m01), bin [n] uint8)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W = img.shape
+        rc = np.ascontiguousarray(rc, dtype=np.int32).reshape(-1, 2)
+        n = len(rc)
+        if n == 0:  # an empty array has no address to pass
+            rc = np.zeros((1, 2), np.int32)
+        mom = np.zeros((max(n, 1), 2), np.int32)
+        b = np.zeros(max(n, 1), np.uint8)
+        _check(self.lib.yv_orient(self.handle, _ptr(img), H, W, W, _ptr(rc), n, _ptr(mom), _ptr(b)), "yv_orient")
+        return mom[:n].copy(), b[:n].copy()
+
     def set_blur_kernel(self, k9: np.ndarray) -> None:
         k = np.ascontiguousarray(k9, dtype=np.uint16).reshape(9)
         _check(self.lib.yv_set_blur_kernel(self.handle, _ptr(k)), "yv_set_blur_kernel")
@@ -686,6 +722,14 @@ class Batch:
         [max_pairs][max_kp] int32, keep [max_pairs][max_kp] uint8."""
         v = _BatchMatch2View()
         _check(self.lib.yv_batch_match2_view_get(self.handle, ctypes.byref(v)), "yv_batch_match2_view_get")
+        return v
+
+
+    def orient_view(self) -> _BatchOrientView:
+        """Device arrays of the keypoints' orientation (yv_batch_orient_view_get; after a run with steering on): bin
+        [max_images + 1][max_kp] uint8, moments [max_images + 1][max_kp][2] int32 (m10, m01), keypoint order."""
+        v = _BatchOrientView()
+        _check(self.lib.yv_batch_orient_view_get(self.handle, ctypes.byref(v)), "yv_batch_orient_view_get")
         return v
 
 

@@ -63,6 +63,12 @@ struct yv_ctx {
     int brief_cap = 0;           // yv_debug_set_brief_workers: a cap on brief_kernel's workers (0: none)
     // keypoint selection before the cut (yv_set_keypoint_select): all off = the reference's cut
     int sel_radius = 0, sel_rows = 0, sel_cols = 0, sel_q = 0;
+    // rotation-steered BRIEF (yv_set_brief_steering): 0 bins = off, the unsteered brief_kernel.  The device tables are
+    // allocated by the first call that switches it on and read by the kernel as they are: a batch keeps no form of
+    // its own of them, so a new table holds for every later launch
+    int steer_bins = 0, steer_radius = 0;
+    int16_t* d_steer_dirs = nullptr;   // [kSteerMaxBins][2]
+    uint32_t* d_steer_addr = nullptr;  // [kSteerMaxBins][256] steer_pack_offsets
 };
 
 namespace yavo {
@@ -127,6 +133,10 @@ struct yv_batch {
     uint64_t* sel_keys = nullptr;   // [max_images][cap] the bucketed candidate lists
     int32_t* sel_starts = nullptr;  // [max_images][kSelMaxCells + 1] the buckets' starts
     uint32_t* sel_counts = nullptr; // [3][max_images] filtered counts after suppression / quota, top-K's unused "seen"
+    // the keypoints' orientation (yv_set_brief_steering): allocated by the first run or call with steering on
+    bool steer_alloc = false;
+    uint8_t* steer_bin = nullptr;   // [slot][max_kp]
+    int32_t* steer_mom = nullptr;   // [slot][max_kp][2] (m10, m01)
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)
@@ -261,7 +271,8 @@ void batch_free(yv_batch* b) {
                     b->match_lim, b->tracks,     b->track_K,  b->T_right,    b->edge_X,    b->edge_uv,
                     b->edge_query, b->edge_count, b->edge_outlier, b->track_inliers,
                     b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep,
-                    b->gates, b->gate_sorted, b->gate_band, b->sel_keys, b->sel_starts, b->sel_counts};
+                    b->gates, b->gate_sorted, b->gate_band, b->sel_keys, b->sel_starts, b->sel_counts,
+                    b->steer_bin, b->steer_mom};
     if (b->bstream) (void)hipStreamSynchronize(b->bstream);
     if (b->side) (void)hipStreamSynchronize(b->side);
     for (void* p : ptrs)
@@ -522,6 +533,43 @@ void launch_select_topk(yv_batch* b, int n_images, int keep, hipStream_t s) {
                       b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
 }
 
+// ---- rotation-steered BRIEF (yv_set_brief_steering) ----
+bool steer_on(const yv_ctx* ctx) { return ctx->steer_bins > 0; }
+
+// the orientation arrays, on first use (zeroed: the carry slot's rows are read before a keypoint was ever carried)
+int ensure_steer(yv_batch* b) {
+    if (b->steer_alloc) return YV_OK;
+    const size_t n = (size_t)b->nslots * (size_t)b->max_kp;
+    int rc = YV_OK;
+    rc |= dalloc(&b->steer_bin, n);
+    rc |= dalloc(&b->steer_mom, 2 * n);
+    if (rc != YV_OK) return YV_ERR_HIP;  // batch_free releases what was allocated
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipMemsetAsync(b->steer_bin, 0, n, s));
+    YV_HIP(hipMemsetAsync(b->steer_mom, 0, 2 * n * sizeof(int32_t), s));
+    YV_HIP(hipStreamSynchronize(s));
+    b->steer_alloc = true;
+    return YV_OK;
+}
+
+// The descriptor stage of n_images images on s: launch_brief, or the steered kernel while steering is on (ensure_steer
+// has passed).
+void launch_describe(yv_batch* b, int n_images, int max_workers, hipStream_t s) {
+    yv_ctx* ctx = b->ctx;
+    if (steer_on(ctx)) {
+        const yavo::SteerTables t{ctx->steer_bins, ctx->steer_radius, ctx->d_steer_dirs, ctx->d_steer_addr};
+        yavo::launch_brief_steer(b->blur, n_images, b->H, b->W, t, b->kp_src, b->kp_count, b->max_kp, b->keypoints,
+                                 b->desc, b->steer_bin, b->steer_mom, s);
+        return;
+    }
+    // the tests' LDS offsets depend on the offsets table and W only: formed again only when the table changed (a
+    // 256-thread launch in the step waited ~15-50 us for a CU behind the side stream's LM, profiles/r06/c17)
+    const bool new_loff = b->loff_version != ctx->offsets_version;
+    b->loff_version = ctx->offsets_version;
+    yavo::launch_brief(b->blur, n_images, b->H, b->W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, b->max_kp,
+                       b->keypoints, b->desc, b->brief_loff, new_loff, b->brief_heads, max_workers, s);
+}
+
 int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
     if (!b->timing || run < 0) return YV_OK;
     if (b->timing == 2 && stage > 1) return YV_OK;  // detect-only: the two events around the detect kernel
@@ -701,6 +749,8 @@ void yv_destroy(yv_ctx* ctx) {
     if (ctx->scratch_h) (void)hipHostFree(ctx->scratch_h);
     if (ctx->fr_ws) (void)hipFree(ctx->fr_ws);
     if (ctx->d_offsets) (void)hipFree(ctx->d_offsets);
+    if (ctx->d_steer_dirs) (void)hipFree(ctx->d_steer_dirs);
+    if (ctx->d_steer_addr) (void)hipFree(ctx->d_steer_addr);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     if (ctx->side) {
@@ -839,6 +889,37 @@ int yv_set_brief_offsets(yv_ctx* ctx, const int8_t* offsets) {
     YV_HIP(hipMemcpyAsync(ctx->d_offsets, offsets, 1024, hipMemcpyHostToDevice, ctx->stream));
     YV_HIP(hipStreamSynchronize(ctx->stream));
     ++ctx->offsets_version;
+    return YV_OK;
+}
+
+int yv_set_brief_steering(yv_ctx* ctx, int n_bins, int radius, const int16_t* dirs, const int8_t* offsets) {
+    if (n_bins < 0 || n_bins > yavo::kSteerMaxBins) return YV_ERR_INVALID;
+    if (n_bins > 0) {
+        if (!dirs || !offsets || radius < 1 || radius > yavo::kSteerMaxRadius) return YV_ERR_INVALID;
+        for (int i = 0; i < 2 * n_bins; ++i)
+            if (dirs[i] < -yavo::kSteerMaxDir || dirs[i] > yavo::kSteerMaxDir) return YV_ERR_INVALID;
+        for (int i = 0; i < 1024 * n_bins; ++i)
+            if (offsets[i] < -yavo::kSteerMaxRadius || offsets[i] > yavo::kSteerMaxRadius) return YV_ERR_INVALID;
+    }
+    if (!ctx) return YV_ERR_INVALID;
+    if (n_bins == 0) {
+        ctx->steer_bins = 0;
+        return YV_OK;
+    }
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    if (!ctx->d_steer_dirs && dalloc(&ctx->d_steer_dirs, 2 * (size_t)yavo::kSteerMaxBins) != YV_OK) return YV_ERR_HIP;
+    if (!ctx->d_steer_addr && dalloc(&ctx->d_steer_addr, 256 * (size_t)yavo::kSteerMaxBins) != YV_OK) return YV_ERR_HIP;
+    std::vector<uint32_t> addr(256 * (size_t)n_bins);
+    yavo::steer_pack_offsets(offsets, 256 * n_bins, addr.data());
+    // a run in flight reads the tables
+    YV_HIP(hipStreamSynchronize(ctx->stream));
+    YV_HIP(hipMemcpyAsync(ctx->d_steer_dirs, dirs, sizeof(int16_t) * 2 * (size_t)n_bins, hipMemcpyHostToDevice,
+                          ctx->stream));
+    YV_HIP(hipMemcpyAsync(ctx->d_steer_addr, addr.data(), sizeof(uint32_t) * addr.size(), hipMemcpyHostToDevice,
+                          ctx->stream));
+    YV_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->steer_bins = n_bins;
+    ctx->steer_radius = radius;
     return YV_OK;
 }
 
@@ -993,6 +1074,13 @@ int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v) {
     return YV_OK;
 }
 
+int yv_batch_orient_view_get(yv_batch* b, yv_batch_orient_view* v) {
+    if (!b || !v || !b->steer_alloc) return YV_ERR_INVALID;
+    v->bin = b->steer_bin;
+    v->moments = b->steer_mom;
+    return YV_OK;
+}
+
 int yv_batch_enable_timing(yv_batch* b, int on) {
     if (!b) return YV_ERR_INVALID;
     if (on && b->events.empty()) {
@@ -1056,6 +1144,8 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     const int keep = std::min(ctx->max_corners, K);
     const int sel = prepare_select(b, H, W);
     if (sel != YV_OK) return sel;
+    const bool steer = steer_on(ctx);
+    if (steer && ensure_steer(b) != YV_OK) return YV_ERR_HIP;
     if (b->pending_carry >= 0 && join_build(b, s) != YV_OK) return YV_ERR_HIP;
     if (b->pending_carry >= 0) {
         const size_t c = (size_t)b->pending_carry, dst = (size_t)b->max_images, nk = (size_t)K;
@@ -1063,6 +1153,11 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
                               hipMemcpyDeviceToDevice, s));
         YV_HIP(hipMemcpyAsync(b->desc + dst * nk, b->desc + c * nk, nk * sizeof(Desc), hipMemcpyDeviceToDevice, s));
         YV_HIP(hipMemcpyAsync(b->kp_count + dst, b->kp_count + c, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if (steer) {  // the carried keypoints' orientation with them
+            YV_HIP(hipMemcpyAsync(b->steer_bin + dst * nk, b->steer_bin + c * nk, nk, hipMemcpyDeviceToDevice, s));
+            YV_HIP(hipMemcpyAsync(b->steer_mom + dst * nk * 2, b->steer_mom + c * nk * 2, nk * 2 * sizeof(int32_t),
+                                  hipMemcpyDeviceToDevice, s));
+        }
         b->pending_carry = -1;
     }
     int run = -1;
@@ -1080,12 +1175,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
     // (its keypoint counts are a copy, kp_count_build, so top-K need not wait)
     rc |= join_build(b, s);
-    // the tests' LDS offsets depend on the offsets table and W only: formed again only when the table changed (a
-    // 256-thread launch in the step waited ~15-50 us for a CU behind the side stream's LM, profiles/r06/c17)
-    const bool new_loff = b->loff_version != ctx->offsets_version;
-    b->loff_version = ctx->offsets_version;
-    yavo::launch_brief(b->blur, n_images, H, W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, K, b->keypoints,
-                       b->desc, b->brief_loff, new_loff, b->brief_heads, brief_workers(ctx, W), s);
+    launch_describe(b, n_images, brief_workers(ctx, W), s);
     rc |= record_stage(b, s, run, 3);
     if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
     b->run_flags = b->n_pairs > 0 ? b->match_flags : 0;
@@ -1604,6 +1694,7 @@ int yv_describe(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const
     if (st != YV_OK) return st;
     yv_batch* b = ctx->single;
     hipStream_t s = ctx->stream;
+    if (steer_on(ctx) && ensure_steer(b) != YV_OK) return YV_ERR_HIP;
     if (upload_image(b, img, stride, s) != YV_OK) return YV_ERR_HIP;
     ctx->h_pinned[0] = n;
     if (n > 0) YV_HIP(stage_h2d(ctx, b->det_rc, rc, sizeof(int32_t) * 2 * (size_t)n, s));
@@ -1611,14 +1702,40 @@ int yv_describe(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const
     yavo::launch_blur9(b->staging, 1, H, W, W, (int64_t)H * W, ctx->k9, b->blur, s);
     yavo::launch_kp_boundary(b->det_rc, b->det_count, 1, H, W, b->max_kp, b->kp_src, b->kp_count, b->kp_band,
                              b->band_off, b->brief_heads, s);
-    const bool new_loff = b->loff_version != ctx->offsets_version;
-    b->loff_version = ctx->offsets_version;
-    yavo::launch_brief(b->blur, 1, H, W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, b->max_kp, b->keypoints,
-                       b->desc, b->brief_loff, new_loff, b->brief_heads, brief_workers(ctx, W), s);
+    launch_describe(b, 1, brief_workers(ctx, W), s);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     st = download_counted(ctx, ctx->h_pinned + 2, b->kp_count, {out, b->keypoints, sizeof(yv_keypoint)}, {}, s);
     if (st != YV_OK) return st;
     *n_out = ctx->h_pinned[2];
+    return YV_OK;
+}
+
+int yv_orient(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const int32_t* rc, int n, int32_t* moments,
+              uint8_t* bin) {
+    if (n < 0 || H < 9 || W < 9 || stride < W || (n > 0 && (!img || !rc || !moments || !bin))) return YV_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (rc[2 * i] < 0 || rc[2 * i] >= H || rc[2 * i + 1] < 0 || rc[2 * i + 1] >= W) return YV_ERR_INVALID;
+    if (n > yavo::kMaxKp) return YV_ERR_CAPACITY;
+    if (!ctx || !steer_on(ctx)) return YV_ERR_INVALID;
+    if (n == 0) return YV_OK;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    int st = ensure_single(ctx, H, W);
+    if (st != YV_OK) return st;
+    yv_batch* b = ctx->single;
+    hipStream_t s = ctx->stream;
+    if (ensure_steer(b) != YV_OK) return YV_ERR_HIP;
+    if (upload_image(b, img, stride, s) != YV_OK) return YV_ERR_HIP;
+    ctx->h_pinned[0] = n;
+    YV_HIP(stage_h2d(ctx, b->det_rc, rc, sizeof(int32_t) * 2 * (size_t)n, s));
+    YV_HIP(stage_h2d(ctx, b->det_count, ctx->h_pinned, sizeof(int32_t), s));
+    yavo::launch_blur9(b->staging, 1, H, W, W, (int64_t)H * W, ctx->k9, b->blur, s);
+    const yavo::SteerTables t{ctx->steer_bins, ctx->steer_radius, ctx->d_steer_dirs, ctx->d_steer_addr};
+    yavo::launch_orient(b->blur, H, W, t, b->det_rc, b->det_count, b->max_kp, b->steer_bin, b->steer_mom, s);
+    if (check_launch() != YV_OK) return YV_ERR_HIP;
+    YV_HIP(stage_d2h(ctx, moments, b->steer_mom, sizeof(int32_t) * 2 * (size_t)n, s));
+    YV_HIP(stage_d2h(ctx, bin, b->steer_bin, (size_t)n, s));
+    YV_HIP(stage_sync(ctx, s));
     return YV_OK;
 }
 

@@ -167,6 +167,28 @@ constexpr int kSelMinCell = 8, kSelMaxCell = 8192;
 uint32_t* launch_select(uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, uint32_t* cand_seen, int n_images,
                         int H, int W, int nms_radius, int cell_rows, int cell_cols, int per_cell, uint64_t* scratch,
                         int32_t* starts, uint32_t* counts, hipStream_t s);
+// Rotation-steered BRIEF (yv_set_brief_steering, yavo_steer.hip): launch_brief's replacement while steering is on.
+// Every sample is the blurred image clamped to [0, H - 1] x [0, W - 1].  The kernel keeps a keypoint's patch in LDS as
+// 2 kSteerMaxRadius + 1 rows of kSteerPatchStride bytes; the offsets table reaches it as one dword per test, the two
+// samples' byte addresses in that patch (steer_pack_offsets: a1 | a2 << 16 of {drow1, dcol1, drow2, dcol2}).
+constexpr int kSteerMaxBins = 64;
+constexpr int kSteerMaxRadius = 15;   // of the moments' disc and of every offset component
+constexpr int kSteerMaxDir = 256;     // |dirs| component bound: 2 * 577,320 * 256 < 2^31
+constexpr int kSteerPatchStride = 40;
+struct SteerTables {
+    int n_bins, radius;
+    const int16_t* dirs;    // [n_bins][2] = (dcol, drow), device
+    const uint32_t* taddr;  // [n_bins][256], device
+};
+void steer_pack_offsets(const int8_t* offsets, int n_tests, uint32_t* out);  // host
+// Records + packed descriptors of kp_src[image][0 .. kp_count[image]) in keypoint order, as launch_brief writes them,
+// and per keypoint bin[image][max_kp] and moments[image][max_kp][2] = (m10, m01).  Reads no band list, no queue head.
+void launch_brief_steer(const uint8_t* blur, int n_images, int H, int W, const SteerTables& t, const int32_t* kp_src,
+                        const int32_t* kp_count, int max_kp, yv_keypoint* keypoints, Desc* desc, uint8_t* bin,
+                        int32_t* moments, hipStream_t s);
+// bin and moments alone of rc[0 .. min(*count, max_kp)) = {row, col}, any position of one H x W image
+void launch_orient(const uint8_t* blur, int H, int W, const SteerTables& t, const int32_t* rc, const int32_t* count,
+                   int max_kp, uint8_t* bin, int32_t* moments, hipStream_t s);
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
