@@ -37,6 +37,7 @@
 #include "../../include/yavo/yavo.h"
 #include "../../include/yavo/yavo_geom.h"
 #include "../../include/yavo/yavo_map.h"
+#include "yavo_host.h"
 #include "yavo_internal.h"
 #include "yavo_se3.h"
 
@@ -1369,7 +1370,7 @@ struct yv_ba {
     int64_t cv_cap = 0;
     yavo::BaParams P;
     yavo::BaMat3 K{};
-    std::vector<void*> owned;
+    yavo::HipOwned mem;  // every d_* / h_* buffer below and P's
     int32_t *d_ep = nullptr, *d_el = nullptr, *d_pe_off = nullptr, *d_pe = nullptr, *d_le_off = nullptr,
             *d_le = nullptr, *d_cv_off = nullptr, *d_cv_e1 = nullptr, *d_cv_e2 = nullptr;
     double* d_meas = nullptr;
@@ -1396,24 +1397,6 @@ constexpr int kBaTickets = 4 + 2 * yavo::ba::kTicketGroups;
 // the global-memory LDLT keeps 2 x 6 np doubles in dynamic LDS beside ~3 KB of its own: 6 x 640 rows fit 64 KB
 constexpr int kBaMaxPoses = 640;
 
-template <class T>
-int ba_alloc(yv_ba* b, T** p, size_t count) {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    if (hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T)) != hipSuccess) {
-        std::fprintf(stderr, "yavo: hipMalloc(%zu B) failed in yv_ba\n", count * sizeof(T));
-        return YV_ERR_HIP;
-    }
-    b->owned.push_back(*p);
-    return YV_OK;
-}
-
-void ba_free_one(yv_ba* b, void* p) {
-    if (!p) return;
-    (void)hipFree(p);
-    b->owned.erase(std::remove(b->owned.begin(), b->owned.end(), p), b->owned.end());
-}
-
 // the tree4096 class totals and per-sum counters of np free poses: P.spart / P.sticket for the Schur tasks (nb upper
 // blocks + np b_schur rows), P.rpart / P.rticket for the pose reduce; grown on demand
 int ba_ensure_schur(yv_ba* b, int np, hipStream_t st) {
@@ -1421,17 +1404,12 @@ int ba_ensure_schur(yv_ba* b, int np, hipStream_t st) {
     if (tasks <= b->schur_cap) return YV_OK;
     if (hipStreamSynchronize(st) != hipSuccess) return YV_ERR_HIP;
     yavo::BaParams& Q = b->P;
-    ba_free_one(b, Q.spart);
-    ba_free_one(b, Q.sticket);
-    ba_free_one(b, Q.rpart);
-    ba_free_one(b, Q.rticket);
-    Q.spart = Q.rpart = nullptr;
-    Q.sticket = Q.rticket = nullptr;
+    b->mem.release(Q.spart, Q.sticket, Q.rpart, Q.rticket);
     b->schur_cap = 0;
-    if (ba_alloc(b, &Q.spart, (size_t)tasks * yavo::ba::kWG * 36) != YV_OK ||
-        ba_alloc(b, &Q.sticket, (size_t)tasks) != YV_OK ||
-        ba_alloc(b, &Q.rpart, (size_t)np * yavo::ba::kWG * 27) != YV_OK ||
-        ba_alloc(b, &Q.rticket, (size_t)np) != YV_OK ||
+    if (b->mem.alloc(&Q.spart, (size_t)tasks * yavo::ba::kWG * 36) != YV_OK ||
+        b->mem.alloc(&Q.sticket, (size_t)tasks) != YV_OK ||
+        b->mem.alloc(&Q.rpart, (size_t)np * yavo::ba::kWG * 27) != YV_OK ||
+        b->mem.alloc(&Q.rticket, (size_t)np) != YV_OK ||
         hipMemsetAsync(Q.sticket, 0, sizeof(unsigned) * tasks, st) != hipSuccess ||
         hipMemsetAsync(Q.rticket, 0, sizeof(unsigned) * (np > 0 ? np : 1), st) != hipSuccess)
         return YV_ERR_HIP;
@@ -1480,53 +1458,50 @@ extern "C" int yv_ba_create(yv_ctx* ctx, int max_poses, int max_landmarks, int m
     const size_t P = max_poses, L = max_landmarks, E = max_edges, ns = 6 * P;
     yavo::BaParams& Q = b->P;
     int rc = YV_OK;
-    rc |= ba_alloc(b, &b->d_ep, E);
-    rc |= ba_alloc(b, &b->d_el, E);
-    rc |= ba_alloc(b, &b->d_meas, 2 * E);
-    rc |= ba_alloc(b, &b->d_pe_off, P + 1);
-    rc |= ba_alloc(b, &b->d_pe, E);
-    rc |= ba_alloc(b, &b->d_le_off, L + 1);
-    rc |= ba_alloc(b, &b->d_le, E);
-    rc |= ba_alloc(b, &b->d_cv_off, P * P + 1);
-    rc |= ba_alloc(b, &Q.poses, 7 * P);
-    rc |= ba_alloc(b, &Q.X, 3 * L);
-    rc |= ba_alloc(b, &Q.poses2, 7 * P);
-    rc |= ba_alloc(b, &Q.X2, 3 * L);
-    rc |= ba_alloc(b, &b->d_cur, 1);
-    rc |= ba_alloc(b, &b->d_ticket, kBaTickets);
-    rc |= ba_alloc(b, &Q.part, 1 + 2 * std::max<size_t>(1, (L + yavo::ba::kNT - 1) / yavo::ba::kNT));
-    rc |= ba_alloc(b, &Q.err, 2 * E);
-    rc |= ba_alloc(b, &Q.Jp, 12 * E);
-    rc |= ba_alloc(b, &Q.Jl, 6 * E);
-    rc |= ba_alloc(b, &Q.Hpp, 36 * P);
-    rc |= ba_alloc(b, &Q.bp, 6 * P);
-    rc |= ba_alloc(b, &Q.Hll, 9 * L);
-    rc |= ba_alloc(b, &Q.bl, 3 * L);
-    rc |= ba_alloc(b, &Q.S, ns * ns);
-    rc |= ba_alloc(b, &Q.bs, ns);
-    rc |= ba_alloc(b, &Q.xp, ns);
-    rc |= ba_alloc(b, &Q.xl, 3 * L);
-    rc |= ba_alloc(b, &Q.tr, ns);
-    rc |= ba_alloc(b, &Q.scal, 16);
-    rc |= ba_alloc(b, &b->d_maxdiag, 1);
-    rc |= ba_alloc(b, &b->d_ctl, 1);
-    if (rc == YV_OK && hipHostMalloc(reinterpret_cast<void**>(&b->h_scal), 4 * sizeof(double)) != hipSuccess)
-        rc = YV_ERR_HIP;
-    if (rc == YV_OK && hipHostMalloc(reinterpret_cast<void**>(&b->h_ctl), sizeof(yavo::BaCtl)) != hipSuccess)
-        rc = YV_ERR_HIP;
-    if (rc == YV_OK && hipHostMalloc(reinterpret_cast<void**>(&b->h_log), sizeof(double) * 65) != hipSuccess)
-        rc = YV_ERR_HIP;
+    rc |= b->mem.alloc(&b->d_ep, E);
+    rc |= b->mem.alloc(&b->d_el, E);
+    rc |= b->mem.alloc(&b->d_meas, 2 * E);
+    rc |= b->mem.alloc(&b->d_pe_off, P + 1);
+    rc |= b->mem.alloc(&b->d_pe, E);
+    rc |= b->mem.alloc(&b->d_le_off, L + 1);
+    rc |= b->mem.alloc(&b->d_le, E);
+    rc |= b->mem.alloc(&b->d_cv_off, P * P + 1);
+    rc |= b->mem.alloc(&Q.poses, 7 * P);
+    rc |= b->mem.alloc(&Q.X, 3 * L);
+    rc |= b->mem.alloc(&Q.poses2, 7 * P);
+    rc |= b->mem.alloc(&Q.X2, 3 * L);
+    rc |= b->mem.alloc(&b->d_cur, 1);
+    rc |= b->mem.alloc(&b->d_ticket, kBaTickets);
+    rc |= b->mem.alloc(&Q.part, 1 + 2 * std::max<size_t>(1, (L + yavo::ba::kNT - 1) / yavo::ba::kNT));
+    rc |= b->mem.alloc(&Q.err, 2 * E);
+    rc |= b->mem.alloc(&Q.Jp, 12 * E);
+    rc |= b->mem.alloc(&Q.Jl, 6 * E);
+    rc |= b->mem.alloc(&Q.Hpp, 36 * P);
+    rc |= b->mem.alloc(&Q.bp, 6 * P);
+    rc |= b->mem.alloc(&Q.Hll, 9 * L);
+    rc |= b->mem.alloc(&Q.bl, 3 * L);
+    rc |= b->mem.alloc(&Q.S, ns * ns);
+    rc |= b->mem.alloc(&Q.bs, ns);
+    rc |= b->mem.alloc(&Q.xp, ns);
+    rc |= b->mem.alloc(&Q.xl, 3 * L);
+    rc |= b->mem.alloc(&Q.tr, ns);
+    rc |= b->mem.alloc(&Q.scal, 16);
+    rc |= b->mem.alloc(&b->d_maxdiag, 1);
+    rc |= b->mem.alloc(&b->d_ctl, 1);
+    if (rc == YV_OK) rc = b->mem.alloc_host(&b->h_scal, 4);
+    if (rc == YV_OK) rc = b->mem.alloc_host(&b->h_ctl, 1);
+    if (rc == YV_OK) rc = b->mem.alloc_host(&b->h_log, 65);
     // sized up front where that is small, so a solve loop's first iterations do not allocate (each growth
     // synchronises the stream and frees device memory, which synchronises the device): the Schur partials of up to 64
     // free poses, the window graph's co-visibility lists (3 per landmark) and a 64-iteration chi2 log
     if (rc == YV_OK && max_poses <= 64) rc |= ba_ensure_schur(b, max_poses, b->st);
     if (rc == YV_OK && max_landmarks > 0) {
-        rc |= ba_alloc(b, &b->d_cv_e1, 3 * L);
-        rc |= ba_alloc(b, &b->d_cv_e2, 3 * L);
+        rc |= b->mem.alloc(&b->d_cv_e1, 3 * L);
+        rc |= b->mem.alloc(&b->d_cv_e2, 3 * L);
         if (rc == YV_OK) b->cv_cap = 3 * (int64_t)L;
     }
     if (rc == YV_OK) {
-        rc |= ba_alloc(b, &b->d_log, 65);
+        rc |= b->mem.alloc(&b->d_log, 65);
         if (rc == YV_OK) b->log_cap = 65;
     }
     if (rc == YV_OK && (hipMemsetAsync(b->d_ticket, 0, kBaTickets * sizeof(unsigned), b->st) != hipSuccess ||
@@ -1548,10 +1523,6 @@ extern "C" void yv_ba_destroy(yv_ba* b) {
     if (!b) return;
     (void)hipSetDevice(b->dev);
     (void)hipStreamSynchronize(b->st);
-    for (void* p : b->owned) (void)hipFree(p);
-    if (b->h_scal) (void)hipHostFree(b->h_scal);
-    if (b->h_ctl) (void)hipHostFree(b->h_ctl);
-    if (b->h_log) (void)hipHostFree(b->h_log);
     delete b;
 }
 
@@ -1619,11 +1590,9 @@ extern "C" int yv_ba_set_problem(yv_ba* b, int n_poses, int n_fixed, int n_landm
                 }
     }
     if (nc > b->cv_cap) {
-        ba_free_one(b, b->d_cv_e1);
-        ba_free_one(b, b->d_cv_e2);
-        b->d_cv_e1 = b->d_cv_e2 = nullptr;
+        b->mem.release(b->d_cv_e1, b->d_cv_e2);
         b->cv_cap = 0;
-        if (ba_alloc(b, &b->d_cv_e1, nc) != YV_OK || ba_alloc(b, &b->d_cv_e2, nc) != YV_OK) return YV_ERR_HIP;
+        if (b->mem.alloc(&b->d_cv_e1, nc) != YV_OK || b->mem.alloc(&b->d_cv_e2, nc) != YV_OK) return YV_ERR_HIP;
         b->cv_cap = nc;
     }
     auto h2d = [&](void* d, const void* h, size_t bytes) {
@@ -1687,14 +1656,11 @@ int ba_solve_enqueue_(yv_ba* b, const double* poses, const double* landmarks, in
     hipStream_t st = b->st;
     if (max_iters + 1 > b->log_cap) {
         if (hipStreamSynchronize(st) != hipSuccess) return YV_ERR_HIP;
-        ba_free_one(b, b->d_log);
-        b->d_log = nullptr;
+        b->mem.release(b->d_log);
         b->log_cap = 0;
-        if (ba_alloc(b, &b->d_log, (size_t)max_iters + 1) != YV_OK) return YV_ERR_HIP;
-        if (b->h_log) (void)hipHostFree(b->h_log);
-        b->h_log = nullptr;
-        if (hipHostMalloc(reinterpret_cast<void**>(&b->h_log), sizeof(double) * (max_iters + 1)) != hipSuccess)
-            return YV_ERR_HIP;
+        if (b->mem.alloc(&b->d_log, (size_t)max_iters + 1) != YV_OK) return YV_ERR_HIP;
+        b->mem.release(b->h_log);
+        if (b->mem.alloc_host(&b->h_log, (size_t)max_iters + 1) != YV_OK) return YV_ERR_HIP;
         b->log_cap = max_iters + 1;
     }
     yavo::BaCtl* c = b->d_ctl;
@@ -1908,12 +1874,10 @@ extern "C" int yv_ba_debug_ldlt(yv_ctx* ctx, const double* S, int n, const doubl
     double *dS = nullptr, *db = nullptr, *dx = nullptr, *ds = nullptr;
     int32_t* dtr = nullptr;
     const size_t nn = (size_t)n * n;
+    yavo::HipOwned mem;  // freed on return
     int rc = YV_OK;
-    if (hipMalloc(reinterpret_cast<void**>(&dS), sizeof(double) * nn) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&db), sizeof(double) * n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&dx), sizeof(double) * n) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&ds), sizeof(double) * 16) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&dtr), sizeof(int32_t) * n) != hipSuccess)
+    if (mem.alloc(&dS, nn) != YV_OK || mem.alloc(&db, (size_t)n) != YV_OK || mem.alloc(&dx, (size_t)n) != YV_OK ||
+        mem.alloc(&ds, 16) != YV_OK || mem.alloc(&dtr, (size_t)n) != YV_OK)
         rc = YV_ERR_HIP;
     double scal[4] = {0, 0, 0, 0};
     if (rc == YV_OK) {
@@ -1937,8 +1901,6 @@ extern "C" int yv_ba_debug_ldlt(yv_ctx* ctx, const double* S, int n, const doubl
                 rc = YV_ERR_HIP;
         }
     }
-    for (void* p : {(void*)dS, (void*)db, (void*)dx, (void*)ds, (void*)dtr})
-        if (p) (void)hipFree(p);
     if (rc == YV_OK) *ok = scal[2] != 0.0 ? 1 : 0;
     return rc;
 }
@@ -2172,6 +2134,7 @@ struct yv_ba_window {
     int32_t *d_cnt = nullptr, *d_edge = nullptr;
     int64_t* d_info = nullptr;  // [1 + 2 max_kf]: n_kf, (frame, count) per keyframe of the last block
     int64_t* h_info = nullptr;  // pinned copy
+    yavo::HipOwned mem;         // the store, d_info / h_info and the event
     hipEvent_t added = nullptr;
     bool add_pending = false;
     std::vector<int32_t> h_cnt;  // per store index, -1 = not recorded
@@ -2185,13 +2148,6 @@ struct yv_ba_window {
 
 namespace {
 
-void win_free_store(yv_ba_window* w) {
-    for (void* p : {(void*)w->d_T, (void*)w->d_X, (void*)w->d_uvo, (void*)w->d_uvp, (void*)w->d_cnt, (void*)w->d_edge})
-        if (p) (void)hipFree(p);
-    w->d_T = w->d_X = w->d_uvo = w->d_uvp = nullptr;
-    w->d_cnt = w->d_edge = nullptr;
-}
-
 // the store covers frames [g0, end): grown by doubling, the recorded frames copied over (stream-ordered)
 int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
     if (w->g0 < 0) w->g0 = first;
@@ -2202,14 +2158,10 @@ int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
     const int64_t M = w->max_lm;
     double *T = nullptr, *X = nullptr, *uvo = nullptr, *uvp = nullptr;
     int32_t *cnt = nullptr, *edge = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&T), sizeof(double) * 7 * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&X), sizeof(double) * 3 * M * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&uvo), sizeof(double) * 2 * M * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&uvp), sizeof(double) * 2 * M * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&cnt), sizeof(int32_t) * cap) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void**>(&edge), sizeof(int32_t) * M * cap) != hipSuccess) {
-        for (void* p : {(void*)T, (void*)X, (void*)uvo, (void*)uvp, (void*)cnt, (void*)edge})
-            if (p) (void)hipFree(p);
+    if (w->mem.alloc(&T, (size_t)(7 * cap)) != YV_OK || w->mem.alloc(&X, (size_t)(3 * M * cap)) != YV_OK ||
+        w->mem.alloc(&uvo, (size_t)(2 * M * cap)) != YV_OK || w->mem.alloc(&uvp, (size_t)(2 * M * cap)) != YV_OK ||
+        w->mem.alloc(&cnt, (size_t)cap) != YV_OK || w->mem.alloc(&edge, (size_t)(M * cap)) != YV_OK) {
+        w->mem.release(T, X, uvo, uvp, cnt, edge);
         return YV_ERR_HIP;
     }
     const int64_t c0 = w->cap;
@@ -2223,7 +2175,7 @@ int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
              hipMemcpyAsync(edge, w->d_edge, sizeof(int32_t) * M * c0, hipMemcpyDeviceToDevice, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
-    win_free_store(w);
+    w->mem.release(w->d_T, w->d_X, w->d_uvo, w->d_uvp, w->d_cnt, w->d_edge);
     w->d_T = T;
     w->d_X = X;
     w->d_uvo = uvo;
@@ -2259,9 +2211,9 @@ extern "C" int yv_ba_window_create(yv_ba* ba, int max_lm, int max_kf, yv_ba_wind
     w->ba = ba;
     w->max_lm = max_lm;
     w->max_kf = max_kf;
-    if (hipMalloc(reinterpret_cast<void**>(&w->d_info), sizeof(int64_t) * (1 + 2 * (size_t)max_kf)) != hipSuccess ||
-        hipHostMalloc(reinterpret_cast<void**>(&w->h_info), sizeof(int64_t) * (1 + 2 * (size_t)max_kf)) != hipSuccess ||
-        hipEventCreateWithFlags(&w->added, hipEventDisableTiming) != hipSuccess) {
+    if (w->mem.alloc(&w->d_info, 1 + 2 * (size_t)max_kf) != YV_OK ||
+        w->mem.alloc_host(&w->h_info, 1 + 2 * (size_t)max_kf) != YV_OK ||
+        w->mem.event(&w->added) != hipSuccess) {
         yv_ba_window_destroy(w);
         return YV_ERR_HIP;
     }
@@ -2272,14 +2224,8 @@ extern "C" int yv_ba_window_create(yv_ba* ba, int max_lm, int max_kf, yv_ba_wind
 extern "C" void yv_ba_window_destroy(yv_ba_window* w) {
     if (!w) return;
     (void)hipSetDevice(w->ba->dev);
-    if (w->added) {
-        (void)hipEventSynchronize(w->added);
-        (void)hipEventDestroy(w->added);
-    }
+    if (w->added) (void)hipEventSynchronize(w->added);
     (void)hipStreamSynchronize(w->ba->st);
-    win_free_store(w);
-    if (w->d_info) (void)hipFree(w->d_info);
-    if (w->h_info) (void)hipHostFree(w->h_info);
     delete w;
 }
 
@@ -2368,11 +2314,9 @@ extern "C" int yv_ba_window_solve_begin(yv_ba_window* w, int64_t first, int n, i
     }
     if (nc > b->cv_cap) {
         if (hipStreamSynchronize(st) != hipSuccess) return YV_ERR_HIP;
-        ba_free_one(b, b->d_cv_e1);
-        ba_free_one(b, b->d_cv_e2);
-        b->d_cv_e1 = b->d_cv_e2 = nullptr;
+        b->mem.release(b->d_cv_e1, b->d_cv_e2);
         b->cv_cap = 0;
-        if (ba_alloc(b, &b->d_cv_e1, nc) != YV_OK || ba_alloc(b, &b->d_cv_e2, nc) != YV_OK) return YV_ERR_HIP;
+        if (b->mem.alloc(&b->d_cv_e1, nc) != YV_OK || b->mem.alloc(&b->d_cv_e2, nc) != YV_OK) return YV_ERR_HIP;
         b->cv_cap = nc;
     }
     b->ready = false;

@@ -1,0 +1,917 @@
+// yavo_batch.hip -- the batched device pipeline of the C ABI (include/yavo/yavo.h): yv_batch_* and the buffers,
+// the match stage and the opt-in stages behind it, which the host-pointer front end (yavo_api.hip) runs on its
+// single-image workspace as well.  Host code only; kernels live in yavo_kernels.hip and its siblings.
+#include "yavo_host.h"
+
+#include <cstdlib>
+
+#include "../../include/yavo/yavo_map.h"
+
+using namespace yavo;
+
+namespace {
+
+constexpr int kEvPerRun = 9;
+constexpr int kMaxTimedRuns = 4096;
+
+// the next writer of what an asynchronous edge build reads (keypoint counts, keypoints, match lists, pairs,
+// tracks) is ordered after it on stream s
+int join_build(yv_batch* b, hipStream_t s) {
+    if (!b->build_pending) return YV_OK;
+    YV_HIP(hipStreamWaitEvent(s, b->ev_built, 0));
+    b->build_pending = false;
+    return YV_OK;
+}
+
+// the swapped pair list of the reverse match
+int upload_pairs_rev(yv_batch* b) {
+    if (!b->m2_alloc || b->n_pairs <= 0) return YV_OK;
+    std::vector<int32_t> r(b->h_pairs.size());
+    for (size_t i = 0; i + 1 < r.size(); i += 2) {
+        r[i] = b->h_pairs[i + 1];
+        r[i + 1] = b->h_pairs[i];
+    }
+    YV_HIP(hipMemcpyAsync(b->pairs_rev, r.data(), sizeof(int32_t) * r.size(), hipMemcpyHostToDevice, b->ctx->stream));
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    return YV_OK;
+}
+
+int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
+    if (!b->timing || run < 0) return YV_OK;
+    if (b->timing == 2 && stage > 1) return YV_OK;  // detect-only: the two events around the detect kernel
+    YV_HIP(hipEventRecord(b->events[(size_t)run * kEvPerRun + stage], s));
+    return YV_OK;
+}
+
+yavo::MatchLists match_lists(const yv_batch* b) { return {b->desc, b->keypoints, b->kp_count, b->max_kp}; }
+
+yavo::MatchRecords match_records(const yv_batch* b) {
+    return {b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj, b->match_lim};
+}
+
+}  // namespace
+
+namespace yavo {
+
+void batch_free(yv_batch* b) {
+    if (!b) return;
+    if (b->bstream) (void)hipStreamSynchronize(b->bstream);
+    if (b->side) (void)hipStreamSynchronize(b->side);
+    if (b->lk) yv_lk_destroy(b->lk);
+    delete b;
+}
+
+static_assert(YV_MATCH_RATIO == yavo::kMatchRatio && YV_MATCH_MUTUAL == yavo::kMatchMutual, "yavo.h / yavo_internal.h");
+static_assert(sizeof(yv_match2) == sizeof(int4), "nn2 is written as int4 {d1, j1, d2, j2}");
+
+// 0 <= flags <= 3 and, with the ratio test, 0 < num <= den <= 32768 (d * den and d * num stay far inside int64, and
+// num <= den makes a tie d1 == d2 fail)
+bool match_filter_args_ok(int flags, int num, int den) {
+    if (flags < 0 || flags > (YV_MATCH_RATIO | YV_MATCH_MUTUAL)) return false;
+    if ((flags & YV_MATCH_RATIO) && !(num > 0 && num <= den && den <= 32768)) return false;
+    return true;
+}
+
+// the match filter's device buffers, on first use
+int ensure_match2(yv_batch* b) {
+    if (b->m2_alloc) return YV_OK;
+    const size_t nk = (size_t)b->max_kp, np = (size_t)std::max(b->max_pairs, 1);
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->match_key2, np * nk);
+    rc |= b->mem.alloc(&b->rev_key, np * nk);
+    rc |= b->mem.alloc(&b->pairs_rev, np * 2);
+    rc |= b->mem.alloc(&b->nn2, np * nk);
+    rc |= b->mem.alloc(&b->rev, np * nk);
+    rc |= b->mem.alloc(&b->keep, np * nk);
+    if (rc != YV_OK) {  // a retry starts clean
+        b->mem.release(b->match_key2, b->rev_key, b->pairs_rev, b->nn2, b->rev, b->keep);
+        return YV_ERR_HIP;
+    }
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipMemsetAsync(b->match_key2, 0xFF, np * nk * sizeof(uint32_t), s));
+    YV_HIP(hipMemsetAsync(b->rev_key, 0xFF, np * nk * sizeof(uint32_t), s));
+    YV_HIP(hipMemsetAsync(b->nn2, 0, np * nk * sizeof(int4), s));
+    YV_HIP(hipMemsetAsync(b->rev, 0xFF, np * nk * sizeof(int32_t), s));
+    YV_HIP(hipMemsetAsync(b->keep, 0, np * nk, s));
+    YV_HIP(hipStreamSynchronize(s));
+    b->m2_alloc = true;
+    return upload_pairs_rev(b);
+}
+
+// {drow_lo, drow_hi, dcol_lo, dcol_hi}: lo <= hi, every bound inside [-65535, 65535]
+bool gate_ok(const int32_t* g) {
+    for (int k = 0; k < 4; ++k)
+        if (g[k] < -yavo::kGateMaxCoord || g[k] > yavo::kGateMaxCoord) return false;
+    return g[0] <= g[1] && g[2] <= g[3];
+}
+
+// the gated matcher's device buffers, on first use (pairs_rev is the match filter's: the reverse launch needs both).
+// The buckets cover max_row + 1 rows and max_col + 1 columns: the widest column cells that keep n_bands * col_cells
+// inside kGateMaxCells, 64 columns at the least.
+int ensure_gates(yv_batch* b, int max_row, int max_col) {
+    if (b->gate_alloc) return YV_OK;
+    const int n_bands = max_row / yavo::kGateBandRows + 1;
+    int shift = 6;
+    while (n_bands * ((max_col >> shift) + 1) > yavo::kGateMaxCells && shift < 16) ++shift;
+    if (n_bands * ((max_col >> shift) + 1) > yavo::kGateMaxCells) return YV_ERR_CAPACITY;
+    const size_t nk = (size_t)b->max_kp, np = (size_t)std::max(b->max_pairs, 1), ns = (size_t)b->nslots;
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->gates, np * 4);
+    rc |= b->mem.alloc(&b->gate_sorted, ns * nk);
+    rc |= b->mem.alloc(&b->gate_band, ns * (size_t)(n_bands + 1));
+    if (rc != YV_OK) {  // a retry starts clean
+        b->mem.release(b->gates, b->gate_sorted, b->gate_band);
+        return YV_ERR_HIP;
+    }
+    b->gate_bands = n_bands;
+    b->gate_cols = (max_col >> shift) + 1;
+    b->gate_shift = shift;
+    b->gate_alloc = true;
+    return YV_OK;
+}
+
+// the quota's cells of an H x W image fit the bucket kernel's counter table
+bool select_fits(const yv_ctx* ctx, int H, int W) {
+    if (ctx->sel_q <= 0) return true;
+    const int64_t cy = (H + ctx->sel_rows - 1) / ctx->sel_rows, cx = (W + ctx->sel_cols - 1) / ctx->sel_cols;
+    return cy * cx <= yavo::kSelMaxCells;
+}
+
+// the selection's device buffers, on first use
+int ensure_select(yv_batch* b) {
+    if (b->sel_alloc) return YV_OK;
+    const size_t ni = (size_t)b->max_images;
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->sel_keys, ni * (size_t)b->cap);
+    rc |= b->mem.alloc(&b->sel_starts, ni * (size_t)(yavo::kSelMaxCells + 1));
+    rc |= b->mem.alloc(&b->sel_counts, 3 * ni);
+    if (rc != YV_OK) {  // a retry starts clean
+        b->mem.release(b->sel_keys, b->sel_starts, b->sel_counts);
+        return YV_ERR_HIP;
+    }
+    b->sel_alloc = true;
+    return YV_OK;
+}
+
+// launch_topk over the detect kernel's lists, behind the context's selection when one is on (select_fits and
+// ensure_select have passed)
+void launch_select_topk(yv_batch* b, int n_images, int keep, hipStream_t s) {
+    const yv_ctx* ctx = b->ctx;
+    uint32_t* count = b->cand_count;
+    uint32_t* seen = b->cand_seen;
+    if (select_on(ctx)) {
+        count = yavo::launch_select(b->cand_keys, b->cap, b->cand_count, b->cand_seen, n_images, b->H, b->W,
+                                    ctx->sel_radius, ctx->sel_rows, ctx->sel_cols, ctx->sel_q, b->sel_keys,
+                                    b->sel_starts, b->sel_counts, s);
+        seen = b->sel_counts + 2 * (size_t)b->max_images;  // the corners before the filter are in cand_seen already
+    }
+    yavo::launch_topk(b->cand_keys, b->cap, count, seen, n_images, b->H, b->W, b->max_kp, keep, b->det_rc, b->det_resp,
+                      b->det_count, b->kp_src, b->kp_count, b->kp_band, b->band_off, b->brief_heads, s);
+}
+
+// ---- rotation-steered BRIEF (yv_set_brief_steering) ----
+// the orientation arrays, on first use (zeroed: the carry slot's rows are read before a keypoint was ever carried)
+int ensure_steer(yv_batch* b) {
+    if (b->steer_alloc) return YV_OK;
+    const size_t n = (size_t)b->nslots * (size_t)b->max_kp;
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->steer_bin, n);
+    rc |= b->mem.alloc(&b->steer_mom, 2 * n);
+    if (rc != YV_OK) {  // a retry starts clean
+        b->mem.release(b->steer_bin, b->steer_mom);
+        return YV_ERR_HIP;
+    }
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipMemsetAsync(b->steer_bin, 0, n, s));
+    YV_HIP(hipMemsetAsync(b->steer_mom, 0, 2 * n * sizeof(int32_t), s));
+    YV_HIP(hipStreamSynchronize(s));
+    b->steer_alloc = true;
+    return YV_OK;
+}
+
+// The descriptor stage of n_images images on s: launch_brief, or the steered kernel while steering is on (ensure_steer
+// has passed).
+void launch_describe(yv_batch* b, int n_images, int max_workers, hipStream_t s) {
+    yv_ctx* ctx = b->ctx;
+    if (steer_on(ctx)) {
+        const yavo::SteerTables t{ctx->steer_bins, ctx->steer_radius, ctx->d_steer_dirs, ctx->d_steer_addr};
+        yavo::launch_brief_steer(b->blur, n_images, b->H, b->W, t, b->kp_src, b->kp_count, b->max_kp, b->keypoints,
+                                 b->desc, b->steer_bin, b->steer_mom, s);
+        return;
+    }
+    // the tests' LDS offsets depend on the offsets table and W only: formed again only when the table changed (a
+    // 256-thread launch in the step waited ~15-50 us for a CU behind the side stream's LM, profiles/r06/c17)
+    const bool new_loff = b->loff_version != ctx->offsets_version;
+    b->loff_version = ctx->offsets_version;
+    yavo::launch_brief(b->blur, n_images, b->H, b->W, ctx->d_offsets, b->kp_src, b->kp_band, b->band_off, b->max_kp,
+                       b->keypoints, b->desc, b->brief_loff, new_loff, b->brief_heads, max_workers, s);
+}
+
+// The selection's preflight of a run on H x W images, before any copy or launch: a refused run leaves the batch as it
+// was.
+int prepare_select(yv_batch* b, int H, int W) {
+    if (!select_on(b->ctx)) return YV_OK;
+    if (!select_fits(b->ctx, H, W)) return YV_ERR_CAPACITY;
+    return ensure_select(b);
+}
+
+// The key buffers ([max_pairs][max_kp], 0xFFFFFFFF = no key) hold keys between the stage's matcher and its finalize
+// only; outside a stage every entry is 0xFFFFFFFF:
+// - yv_batch_create fills match_key, ensure_match2 fills match_key2 and rev_key (and the swapped pair list pairs_rev).
+// - A matcher stores a key for every query of every pair, [0, nq): the forward one into match_key (top2: and
+//   match_key2), the one over the swapped pairs, whose queries are the train points, into rev_key [0, nt).
+// - The finalize reads and resets match_key [0, nq); the filtering one also match_key2 [0, nq) and rev_key [0, nt),
+//   whether or not the swapped pairs ran (it then reads "no query" for every train point).
+// So a stage with top2 ends in the filtering finalize and one without in the plain one, and no stage sees the keys of
+// an earlier one, however the lists' lengths changed.  Stage event 4 separates matcher and finalize (run < 0: none).
+int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run) {
+    const yavo::MatchLists lists = match_lists(b);
+    uint32_t* key2 = st.top2 ? b->match_key2 : nullptr;
+    if (st.gated) {
+        yavo::launch_gate_sort(b->keypoints, b->kp_count, b->nslots, b->max_kp, b->gate_bands, b->gate_cols,
+                               b->gate_shift, b->gate_sorted, b->gate_band, s);
+        yavo::launch_match_gated(lists, b->pairs, st.n_pairs, b->gate_bands, b->gate_sorted, b->gate_band, b->gates,
+                                 false, b->match_key, key2, s);
+        if (st.with_rev)
+            yavo::launch_match_gated(lists, b->pairs_rev, st.n_pairs, b->gate_bands, b->gate_sorted, b->gate_band,
+                                     b->gates, true, b->rev_key, nullptr, s);
+    } else {
+        yavo::launch_match(lists, b->pairs, st.n_pairs, st.max_train, b->match_key, key2, s);
+        if (st.with_rev) yavo::launch_match(lists, b->pairs_rev, st.n_pairs, st.max_train_rev, b->rev_key, nullptr, s);
+    }
+    const int rc = record_stage(b, s, run, 4);
+    const yavo::FinalizeRobust rb{b->match_key2, b->rev_key, st.flags, st.num, st.den, b->nn2, b->rev, b->keep};
+    yavo::launch_match_finalize(b->match_key, lists, b->pairs, st.n_pairs, st.thr, match_records(b),
+                                st.top2 ? &rb : nullptr, s, st.kp_count_copy, st.n_slots);
+    return rc;
+}
+
+}  // namespace yavo
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------------------
+// batches
+// ------------------------------------------------------------------------------------------------
+int yv_batch_create(yv_ctx* ctx, int max_images, int H, int W, int max_kp, int max_pairs, yv_batch** out) {
+    if (!ctx || !out || max_images <= 0 || H < 9 || W < 9 || max_kp <= 0 || max_kp > yavo::kMaxKp ||
+        max_pairs < 0 || (int64_t)H * W >= (1ll << 31))
+        return YV_ERR_INVALID;
+    if (W > yavo::kMaxWidth) return YV_ERR_CAPACITY;  // BRIEF stages 49 image rows in LDS
+    if (H > yavo::kBandRows * yavo::kMaxBands) return YV_ERR_CAPACITY;  // top-K's band lists
+    *out = nullptr;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    yv_batch* b = new (std::nothrow) yv_batch();
+    if (!b) return YV_ERR_INVALID;
+    b->ctx = ctx;
+    b->max_images = max_images;
+    b->H = H;
+    b->W = W;
+    b->max_kp = max_kp;
+    b->max_pairs = max_pairs;
+    b->nslots = max_images + 1;
+    b->cap = (int64_t)(H - 8) * (W - 8);  // every pixel FAST can test: no candidate is ever dropped
+    const size_t ns = (size_t)b->nslots, nk = (size_t)max_kp, np = (size_t)std::max(max_pairs, 1);
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->cand_keys, (size_t)max_images * (size_t)b->cap);
+    rc |= b->mem.alloc(&b->cand_count, ns);
+    rc |= b->mem.alloc(&b->cand_seen, ns);
+    rc |= b->mem.alloc(&b->det_rc, ns * nk * 2);
+    rc |= b->mem.alloc(&b->det_resp, ns * nk);
+    rc |= b->mem.alloc(&b->det_count, ns);
+    rc |= b->mem.alloc(&b->kp_src, ns * nk * 4);
+    rc |= b->mem.alloc(&b->kp_count, ns);
+    rc |= b->mem.alloc(&b->kp_count_build, ns);
+    rc |= b->mem.alloc(&b->kp_band, ns * nk * 4);
+    rc |= b->mem.alloc(&b->band_off, ns * (size_t)(yavo::kMaxBands + 1));
+    rc |= b->mem.alloc(&b->brief_loff, 512);
+    rc |= b->mem.alloc(&b->brief_heads, (size_t)yavo::kBriefHeads);
+    rc |= b->mem.alloc(&b->keypoints, ns * nk);
+    rc |= b->mem.alloc(&b->desc, ns * nk);
+    rc |= b->mem.alloc(&b->blur, (size_t)max_images * (size_t)yavo::blur_image_bytes(H, W));
+    rc |= b->mem.alloc(&b->pairs, np * 2);
+    rc |= b->mem.alloc(&b->match_key, np * nk);
+    rc |= b->mem.alloc(&b->matches, np * nk);
+    rc |= b->mem.alloc(&b->match_count, np);
+    rc |= b->mem.alloc(&b->filtered, np * nk);
+    rc |= b->mem.alloc(&b->filt_count, np);
+    rc |= b->mem.alloc(&b->match_dj, np * nk);
+    rc |= b->mem.alloc(&b->match_lim, np);
+    rc |= b->mem.alloc(&b->staging, (size_t)H * W);
+    if (rc != YV_OK) {
+        batch_free(b);
+        return YV_ERR_HIP;
+    }
+    hipStream_t s = ctx->stream;
+    bool ok = hipMemsetAsync(b->cand_count, 0, ns * sizeof(uint32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->cand_seen, 0, ns * sizeof(uint32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->kp_count, 0, ns * sizeof(int32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->det_count, 0, ns * sizeof(int32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->match_key, 0xFF, np * nk * sizeof(uint32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->keypoints, 0, ns * nk * sizeof(yv_keypoint), s) == hipSuccess &&
+              hipMemsetAsync(b->match_count, 0, np * sizeof(int32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->filt_count, 0, np * sizeof(int32_t), s) == hipSuccess &&
+              hipMemsetAsync(b->match_lim, 0, np * sizeof(int32_t), s) == hipSuccess &&
+              hipStreamSynchronize(s) == hipSuccess;
+    if (!ok) {
+        batch_free(b);
+        return YV_ERR_HIP;
+    }
+    *out = b;
+    return YV_OK;
+}
+
+void yv_batch_destroy(yv_batch* b) {
+    if (!b) return;
+    (void)hipSetDevice(b->ctx->device);
+    (void)hipStreamSynchronize(b->ctx->stream);
+    batch_free(b);
+}
+
+int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs, int n_pairs) {
+    if (!b || n_pairs < 0 || n_pairs > b->max_pairs || (n_pairs > 0 && !pairs)) return YV_ERR_INVALID;
+    for (int i = 0; i < 2 * n_pairs; ++i)
+        if (pairs[i] < 0 || pairs[i] > b->max_images) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // an edge build in flight reads pairs
+    b->build_pending = false;
+    if (n_pairs > 0) {
+        YV_HIP(hipMemcpyAsync(b->pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice,
+                              b->ctx->stream));
+        YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    }
+    b->h_pairs.assign(pairs, pairs + 2 * (size_t)n_pairs);
+    b->n_pairs = n_pairs;
+    b->n_tracks = 0;  // tracks refer to pair indices: set them again
+    b->gated = false;  // and so do the gates
+    return upload_pairs_rev(b);
+}
+
+int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates, int n_pairs) {
+    if (!b) return YV_ERR_INVALID;
+    if (!gates || n_pairs == 0) {
+        b->gated = false;
+        return YV_OK;
+    }
+    if (n_pairs != b->n_pairs) return YV_ERR_INVALID;
+    for (int p = 0; p < n_pairs; ++p)
+        if (!gate_ok(gates + 4 * p)) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    const int rc = ensure_gates(b, b->H - 1, b->W - 1);
+    if (rc != YV_OK) return rc;
+    // a run in flight reads the table
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    YV_HIP(hipMemcpyAsync(b->gates, gates, sizeof(int32_t) * 4 * (size_t)n_pairs, hipMemcpyHostToDevice,
+                          b->ctx->stream));
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    b->gated = true;
+    return YV_OK;
+}
+
+int yv_batch_set_match_filter(yv_batch* b, int flags, int ratio_num, int ratio_den) {
+    if (!match_filter_args_ok(flags, ratio_num, ratio_den) || !b) return YV_ERR_INVALID;
+    if (flags != 0) {
+        if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+        const int rc = ensure_match2(b);
+        if (rc != YV_OK) return rc;
+    }
+    b->match_flags = flags;
+    b->ratio_num = (flags & YV_MATCH_RATIO) ? ratio_num : 0;
+    b->ratio_den = (flags & YV_MATCH_RATIO) ? ratio_den : 1;
+    return YV_OK;
+}
+
+int yv_batch_match2_view_get(yv_batch* b, yv_batch_match2_view* v) {
+    if (!b || !v || !b->m2_alloc) return YV_ERR_INVALID;
+    v->nn2 = reinterpret_cast<const yv_match2*>(b->nn2);
+    v->rev = b->rev;
+    v->keep = b->keep;
+    return YV_OK;
+}
+
+int yv_batch_orient_view_get(yv_batch* b, yv_batch_orient_view* v) {
+    if (!b || !v || !b->steer_alloc) return YV_ERR_INVALID;
+    v->bin = b->steer_bin;
+    v->moments = b->steer_mom;
+    return YV_OK;
+}
+
+int yv_batch_enable_timing(yv_batch* b, int on) {
+    if (!b) return YV_ERR_INVALID;
+    if (on && b->events.empty()) {
+        if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+        b->events.resize((size_t)kMaxTimedRuns * kEvPerRun);
+        for (auto& e : b->events) YV_HIP(b->mem.event(&e, hipEventDefault));
+        b->tracked.assign(kMaxTimedRuns, 0);
+    }
+    b->timing = on == 2 ? 2 : (on != 0 ? 1 : 0);
+    b->runs_recorded = 0;
+    b->last_run = -1;
+    std::fill(b->tracked.begin(), b->tracked.end(), 0);
+    return YV_OK;
+}
+
+int yv_batch_stage_times(yv_batch* b, float* ms, int* n_runs) {
+    if (!b || !ms) return YV_ERR_INVALID;
+    for (int i = 0; i < 8; ++i) ms[i] = 0.f;
+    const int runs = std::min(b->runs_recorded, kMaxTimedRuns);
+    if (n_runs) *n_runs = runs;
+    if (runs == 0) return YV_OK;
+    for (int r = 0; r < runs; ++r) {
+        const hipEvent_t* ev = &b->events[(size_t)r * kEvPerRun];
+        if (b->timing == 2) {
+            float t = 0.f;
+            YV_HIP(hipEventSynchronize(ev[1]));
+            YV_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
+            ms[0] += t;
+            continue;
+        }
+        YV_HIP(hipEventSynchronize(ev[b->tracked[r] ? 8 : 5]));
+        for (int st = 0; st < 5; ++st) {
+            float t = 0.f;
+            YV_HIP(hipEventElapsedTime(&t, ev[st], ev[st + 1]));
+            ms[st] += t;
+        }
+        if (b->tracked[r])
+            for (int st = 5; st < 7; ++st) {
+                float t = 0.f;
+                YV_HIP(hipEventElapsedTime(&t, ev[st + 1], ev[st + 2]));
+                ms[st] += t;
+            }
+    }
+    return YV_OK;
+}
+
+namespace {
+int launch_deferred_after(yv_batch* b, hipStream_t s);
+int flush_deferred(yv_batch* b);
+}  // namespace
+
+int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride, int64_t image_pitch, int match_thr,
+                 int carry_from, void* stream) {
+    if (!b || !d_images || n_images <= 0 || n_images > b->max_images || stride < b->W ||
+        image_pitch < (int64_t)stride * (b->H - 1) + b->W || carry_from >= n_images)
+        return YV_ERR_INVALID;
+    yv_ctx* ctx = b->ctx;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+    const int H = b->H, W = b->W, K = b->max_kp;
+    const int keep = std::min(ctx->max_corners, K);
+    const int sel = prepare_select(b, H, W);
+    if (sel != YV_OK) return sel;
+    const bool steer = steer_on(ctx);
+    if (steer && ensure_steer(b) != YV_OK) return YV_ERR_HIP;
+    if (b->pending_carry >= 0 && join_build(b, s) != YV_OK) return YV_ERR_HIP;
+    if (b->pending_carry >= 0) {
+        const size_t c = (size_t)b->pending_carry, dst = (size_t)b->max_images, nk = (size_t)K;
+        YV_HIP(hipMemcpyAsync(b->keypoints + dst * nk, b->keypoints + c * nk, nk * sizeof(yv_keypoint),
+                              hipMemcpyDeviceToDevice, s));
+        YV_HIP(hipMemcpyAsync(b->desc + dst * nk, b->desc + c * nk, nk * sizeof(Desc), hipMemcpyDeviceToDevice, s));
+        YV_HIP(hipMemcpyAsync(b->kp_count + dst, b->kp_count + c, sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+        if (steer) {  // the carried keypoints' orientation with them
+            YV_HIP(hipMemcpyAsync(b->steer_bin + dst * nk, b->steer_bin + c * nk, nk, hipMemcpyDeviceToDevice, s));
+            YV_HIP(hipMemcpyAsync(b->steer_mom + dst * nk * 2, b->steer_mom + c * nk * 2, nk * 2 * sizeof(int32_t),
+                                  hipMemcpyDeviceToDevice, s));
+        }
+        b->pending_carry = -1;
+    }
+    int run = -1;
+    if (b->timing && b->runs_recorded < kMaxTimedRuns) run = b->runs_recorded++;
+    b->last_run = run;
+    int rc = YV_OK;
+    rc |= record_stage(b, s, run, 0);
+    yavo::launch_detect_blur(d_images, n_images, H, W, stride, image_pitch, ctx->fast_thr, ctx->harris_eigen, b->cand_keys, b->cap,
+                             b->cand_count, ctx->k9, b->blur, s);
+    rc |= record_stage(b, s, run, 1);
+    if (b->overlap_mode == 2) rc |= launch_deferred_after(b, s);
+    launch_select_topk(b, n_images, keep, s);
+    rc |= record_stage(b, s, run, 2);
+    if (b->overlap_mode == 4) rc |= launch_deferred_after(b, s);  // after top-K
+    // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
+    // (its keypoint counts are a copy, kp_count_build, so top-K need not wait)
+    rc |= join_build(b, s);
+    launch_describe(b, n_images, brief_workers(ctx, W), s);
+    rc |= record_stage(b, s, run, 3);
+    if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
+    b->run_flags = b->n_pairs > 0 ? b->match_flags : 0;
+    // the asynchronous edge build reads a copy of the keypoint counts (the next run's top-K rewrites them):
+    // the finalize kernel writes it, where a separate device copy waited ~50 us for a CU at the end of the step
+    const bool copy_counts = b->n_pairs > 0 && b->overlap && b->build_async && b->lk_step == 0;
+    if (b->n_pairs > 0) {
+        // with the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
+        MatchStage st;
+        st.n_pairs = b->n_pairs;
+        st.max_train = st.max_train_rev = K;
+        st.top2 = b->run_flags != 0;
+        st.with_rev = st.top2 && (b->match_flags & YV_MATCH_MUTUAL) != 0;
+        st.gated = b->gated;
+        st.thr = match_thr;
+        st.flags = b->match_flags;
+        st.num = b->ratio_num;
+        st.den = b->ratio_den;
+        st.kp_count_copy = copy_counts ? b->kp_count_build : nullptr;
+        st.n_slots = b->nslots;
+        rc |= match_stage(b, st, s, run);
+    } else {
+        rc |= record_stage(b, s, run, 4);
+    }
+    b->counts_copied = copy_counts;
+    rc |= record_stage(b, s, run, 5);
+    if (rc != YV_OK) return YV_ERR_HIP;
+    // The carry slot keeps this run's frame k-1 (the query of its first temporal pair) until the next run
+    // starts, so yv_batch_track and the view still see it; the copy of image carry_from is deferred.
+    b->pending_carry = carry_from;
+    b->run_images = d_images;
+    b->run_n = n_images;
+    b->run_stride = stride;
+    b->run_pitch = image_pitch;
+    return check_launch();
+}
+
+int yv_batch_view_get(yv_batch* b, yv_batch_view* v) {
+    if (!b || !v) return YV_ERR_INVALID;
+    v->max_images = b->max_images;
+    v->max_kp = b->max_kp;
+    v->max_pairs = b->max_pairs;
+    v->H = b->H;
+    v->W = b->W;
+    v->cand_cap = b->cap;
+    v->cand_count = b->cand_seen;
+    v->det_count = b->det_count;
+    v->det_rc = b->det_rc;
+    v->det_resp = b->det_resp;
+    v->kp_count = b->kp_count;
+    v->keypoints = b->keypoints;
+    v->blurred = b->blur;
+    v->blur_pitch = yavo::blur_pitch(b->W);
+    v->match_count = b->match_count;
+    v->matches = b->matches;
+    v->filt_count = b->filt_count;
+    v->filtered = b->filtered;
+    v->match_dj = reinterpret_cast<const int32_t*>(b->match_dj);
+    v->match_lim = b->match_lim;
+    v->n_tracks = b->n_tracks;
+    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp, k = (size_t)b->tbuf;
+    v->edge_count = b->edge_count ? b->edge_count + k * nt : nullptr;
+    v->edge_X = b->edge_X ? b->edge_X + k * nt * nk * 3 : nullptr;
+    v->edge_uv = b->edge_uv ? b->edge_uv + k * nt * nk * 2 : nullptr;
+    v->edge_query = b->edge_query ? b->edge_query + k * nt * nk : nullptr;
+    v->edge_outlier = b->edge_outlier ? b->edge_outlier + k * nt * nk : nullptr;
+    v->track_inliers = b->track_inliers ? b->track_inliers + k * nt : nullptr;
+    return YV_OK;
+}
+
+int yv_batch_set_tracks(yv_batch* b, const int32_t* tracks, int n_tracks, const double K[9], const double T_right[7]) {
+    if (!b || n_tracks < 0 || (n_tracks > 0 && (!tracks || !K || !T_right))) return YV_ERR_INVALID;
+    for (int t = 0; t < n_tracks; ++t) {
+        const int sp = tracks[2 * t], tp = tracks[2 * t + 1];
+        if (sp < 0 || sp >= b->n_pairs) return YV_ERR_INVALID;
+        if (b->lk_step > 0) {
+            // LK mode: {stereo pair of frame k-1, image of frame k}, both LK images (multiples of the step)
+            const int prev = b->h_pairs[2 * sp];
+            if (prev % b->lk_step || prev >= b->max_images || tp < 0 || tp >= b->max_images || tp % b->lk_step)
+                return YV_ERR_INVALID;
+        } else {
+            if (tp < 0 || tp >= b->n_pairs) return YV_ERR_INVALID;
+            if (b->h_pairs[2 * sp] != b->h_pairs[2 * tp + 1]) return YV_ERR_INVALID;  // stereo query = temporal train
+        }
+    }
+    for (int i = 0; i < 9 && n_tracks > 0; ++i)
+        if (!std::isfinite(K[i])) return YV_ERR_INVALID;
+    if (n_tracks > 0 && !finite_pose(T_right)) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = b->ctx->stream;
+    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // a build in flight reads tracks / K
+    b->build_pending = false;
+    if (b->side) YV_HIP(hipStreamSynchronize(b->side));  // an LM in flight reads tracks / K
+    if (n_tracks > b->max_tracks) {
+        YV_HIP(hipStreamSynchronize(s));
+        if (b->side) YV_HIP(hipStreamSynchronize(b->side));
+        b->track_mem.clear();
+        b->max_tracks = 0;
+        b->n_tracks = 0;
+        const size_t nt = (size_t)n_tracks, nk = (size_t)b->max_kp;
+        int rc = YV_OK;
+        rc |= b->track_mem.alloc(&b->tracks, 2 * nt);
+        rc |= b->track_mem.alloc(&b->track_K, 9 * nt);
+        rc |= b->track_mem.alloc(&b->T_right, 7);
+        rc |= b->track_mem.alloc(&b->edge_X, kEdgeBufs * 3 * nt * nk);
+        rc |= b->track_mem.alloc(&b->edge_uv, kEdgeBufs * 2 * nt * nk);
+        rc |= b->track_mem.alloc(&b->edge_query, kEdgeBufs * nt * nk);
+        rc |= b->track_mem.alloc(&b->edge_count, kEdgeBufs * nt);
+        rc |= b->track_mem.alloc(&b->edge_outlier, kEdgeBufs * nt * nk);
+        rc |= b->track_mem.alloc(&b->track_inliers, kEdgeBufs * nt);
+        rc |= b->track_mem.alloc(&b->lk_sp, nt);
+        rc |= b->track_mem.alloc(&b->lk_pairs, 2 * nt);
+        rc |= b->track_mem.alloc(&b->lk_X, 2 * 3 * nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_pts, 2 * 2 * nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_next, 2 * nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_err, nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_status, nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_q, 2 * nt * nk);
+        rc |= b->track_mem.alloc(&b->lk_count, 2 * nt);
+        b->lk_ev_pending[0] = b->lk_ev_pending[1] = false;
+        if (rc != YV_OK) return YV_ERR_HIP;
+        b->max_tracks = n_tracks;
+    }
+    if (n_tracks > 0) {
+        std::vector<double> Ks(9 * (size_t)n_tracks);
+        for (int t = 0; t < n_tracks; ++t) std::memcpy(&Ks[9 * (size_t)t], K, 9 * sizeof(double));
+        YV_HIP(hipMemcpyAsync(b->tracks, tracks, 2 * sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, s));
+        YV_HIP(hipMemcpyAsync(b->track_K, Ks.data(), Ks.size() * sizeof(double), hipMemcpyHostToDevice, s));
+        YV_HIP(hipMemcpyAsync(b->T_right, T_right, 7 * sizeof(double), hipMemcpyHostToDevice, s));
+        YV_HIP(hipMemsetAsync(b->edge_count, 0, kEdgeBufs * sizeof(int32_t) * (size_t)b->max_tracks, s));
+        if (b->lk_step > 0) {
+            std::vector<int32_t> sp(n_tracks), lp(2 * (size_t)n_tracks);
+            for (int t = 0; t < n_tracks; ++t) {
+                sp[t] = tracks[2 * t];
+                lp[2 * t] = b->h_pairs[2 * sp[t]] / b->lk_step;
+                lp[2 * t + 1] = tracks[2 * t + 1] / b->lk_step;
+            }
+            YV_HIP(hipMemcpyAsync(b->lk_sp, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, s));
+            YV_HIP(hipMemcpyAsync(b->lk_pairs, lp.data(), sizeof(int32_t) * lp.size(), hipMemcpyHostToDevice, s));
+        }
+        YV_HIP(hipStreamSynchronize(s));
+    }
+    b->n_tracks = n_tracks;
+    return YV_OK;
+}
+
+namespace {
+
+struct MapArgs {
+    int64_t first_frame;
+    int kf_every, max_kf;
+    void* block;
+};
+
+int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream, const MapArgs* map);
+
+// The pose LM (and the map block) of one track. Overlap: on the side stream after the edge build (ev_edges[k]);
+// otherwise on `s`, in order.
+int launch_lm(yv_batch* b, const yv_batch::DeferredLM& L, hipStream_t s) {
+    const int k = L.k;
+    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
+    double* eX = b->edge_X + k * nt * nk * 3;
+    double* euv = b->edge_uv + k * nt * nk * 2;
+    int32_t* ec = b->edge_count + k * nt;
+    uint8_t* eo = b->edge_outlier + k * nt * nk;
+    int32_t* inl = b->track_inliers + k * nt;
+    hipStream_t ls = s;
+    if (b->overlap) {
+        // the LM reads only this track's edge buffer, priors and poses: it runs on the side stream beside the
+        // next batch's image kernels (which overwrite keypoints / matches, already consumed by the build)
+        YV_HIP(hipStreamWaitEvent(b->side, b->ev_edges[k], 0));
+        ls = b->side;
+    }
+    if (L.ev) YV_HIP(hipEventRecord(L.ev[7], ls));
+    yavo::launch_track_pose(b->n_tracks, ec, b->max_kp, eX, euv, b->track_K, L.priors, L.poses, eo, inl, ls);
+    if (L.ev) {
+        YV_HIP(hipEventRecord(L.ev[8], ls));
+        b->tracked[L.run] = 1;
+    }
+    if (L.has_map) {
+        // the chunk's map block, after the LM on its stream: the build that next rewrites this edge buffer waits
+        // for ev_lm[k], recorded below, so it also waits for these reads. The block itself is rewritten only
+        // after its last reader released it (the all-gather of the previous chunk, yv_batch_map_release).
+        if (b->map_release_pending) {
+            YV_HIP(hipStreamWaitEvent(ls, b->ev_map_release, 0));
+            b->map_release_pending = false;
+        }
+        yavo::launch_map_chunk(L.poses, b->n_tracks, L.first_frame, L.kf_every, ec, eX, eo, b->max_kp, L.max_kf,
+                               L.block, ls);
+        if (!b->ev_map) YV_HIP(b->mem.event(&b->ev_map));
+        YV_HIP(hipEventRecord(b->ev_map, ls));
+        b->map_written = true;
+    }
+    if (b->overlap) {
+        YV_HIP(hipEventRecord(b->ev_lm[k], ls));
+        b->lm_pending[k] = true;
+    }
+    return YV_OK;
+}
+
+// The deferred LM of the previous track, ordered after the work issued on s so far (the stage it waits for).
+int launch_deferred_after(yv_batch* b, hipStream_t s) {
+    if (!b->deferred.active) return YV_OK;
+    if (!b->ev_defer) YV_HIP(b->mem.event(&b->ev_defer));
+    YV_HIP(hipEventRecord(b->ev_defer, s));
+    YV_HIP(hipStreamWaitEvent(b->side, b->ev_defer, 0));
+    b->deferred.active = false;
+    return launch_lm(b, b->deferred, s) == YV_OK ? YV_OK : YV_ERR_HIP;
+}
+
+// Launch a deferred LM now (its inputs are complete once ev_edges was recorded).
+int flush_deferred(yv_batch* b) {
+    if (!b->deferred.active) return YV_OK;
+    b->deferred.active = false;
+    return launch_lm(b, b->deferred, b->ctx->stream);
+}
+
+}  // namespace
+
+int yv_batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream) {
+    return batch_track(b, d_priors, d_poses, stream, nullptr);
+}
+
+int yv_batch_track_map(yv_batch* b, const double* d_priors, double* d_poses, int64_t first_frame, int kf_every,
+                       void* d_block, int max_kf, void* stream) {
+    if (!b || !d_block || kf_every < 1 || max_kf < 1 || first_frame < 0) return YV_ERR_INVALID;
+    const MapArgs m{first_frame, kf_every, max_kf, d_block};
+    return batch_track(b, d_priors, d_poses, stream, &m);
+}
+
+int yv_batch_map_wait(yv_batch* b, void* stream) {
+    if (!b || !stream) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;  // the block is written after the LM
+    if (!b->map_written) return YV_OK;
+    YV_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), b->ev_map, 0));
+    return YV_OK;
+}
+
+int yv_batch_map_release(yv_batch* b, void* stream) {
+    if (!b || !stream) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (!b->ev_map_release) YV_HIP(b->mem.event(&b->ev_map_release));
+    YV_HIP(hipEventRecord(b->ev_map_release, reinterpret_cast<hipStream_t>(stream)));
+    b->map_release_pending = true;
+    return YV_OK;
+}
+
+namespace {
+
+int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream, const MapArgs* map) {
+    if (!b || (b->n_tracks > 0 && (!d_priors || !d_poses))) return YV_ERR_INVALID;
+    if (b->n_tracks == 0) return YV_OK;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : b->ctx->stream;
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;  // two tracks without a run between them
+    const int k = b->track_calls++ % kEdgeBufs;
+    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
+    double* eX = b->edge_X + k * nt * nk * 3;
+    double* euv = b->edge_uv + k * nt * nk * 2;
+    int32_t* eq = b->edge_query + k * nt * nk;
+    int32_t* ec = b->edge_count + k * nt;
+    const int run = b->last_run;
+    const bool timed = b->timing == 1 && run >= 0 && !b->tracked[run];
+    hipEvent_t* ev = timed ? &b->events[(size_t)run * kEvPerRun] : nullptr;
+    const hipStream_t s_run = s;
+    double* lkX = nullptr;
+    float* lkP = nullptr;
+    int32_t *lkQ = nullptr, *lkC = nullptr;
+    int lk_j = 0;
+    if (b->lk_step > 0) {
+        // LK: frame k-1's stereo map points from this run's keypoints / matches, on the run's stream (the next run
+        // rewrites them), into the point set the LK stage two tracks ago has finished reading
+        if (!b->run_images || b->run_n < b->lk_step) return YV_ERR_INVALID;
+        lk_j = b->lk_set;
+        b->lk_set ^= 1;
+        lkX = b->lk_X + (size_t)lk_j * nt * nk * 3;
+        lkP = b->lk_pts + (size_t)lk_j * nt * nk * 2;
+        lkQ = b->lk_q + (size_t)lk_j * nt * nk;
+        lkC = b->lk_count + (size_t)lk_j * nt;
+        if (b->lk_ev_pending[lk_j]) YV_HIP(hipStreamWaitEvent(s_run, b->ev_lk[lk_j], 0));
+        b->lk_ev_pending[lk_j] = false;
+        yavo::launch_stereo_points(b->lk_sp, b->n_tracks, b->pairs, b->keypoints, b->kp_count, b->match_dj,
+                                   b->match_lim, b->max_kp, b->track_K, b->T_right, lkX, lkP, lkQ, lkC, s_run,
+                                   b->run_flags ? b->keep : nullptr);
+    }
+    const int32_t* build_counts = b->kp_count;
+    if (b->overlap && b->build_async) {
+        // the build (match: edges from the run's matches; LK: pyramids, flow, edges) waits for the run on s and
+        // leaves s free for the next run's detect; the match build reads a copy of the keypoint counts
+        if (b->lk_step == 0) {
+            if (!b->counts_copied)
+                YV_HIP(hipMemcpyAsync(b->kp_count_build, b->kp_count, sizeof(int32_t) * (size_t)b->nslots,
+                                      hipMemcpyDeviceToDevice, s_run));
+            build_counts = b->kp_count_build;
+        }
+        YV_HIP(hipEventRecord(b->ev_fin, s_run));
+        YV_HIP(hipStreamWaitEvent(b->bstream, b->ev_fin, 0));
+        s = b->bstream;
+    }
+    // buffer k was last read by the LM kEdgeBufs tracks ago (side stream): the build must not overwrite it early
+    if (b->lm_pending[k]) YV_HIP(hipStreamWaitEvent(s, b->ev_lm[k], 0));
+    if (timed) YV_HIP(hipEventRecord(ev[6], s));
+    if (b->lk_step > 0) {
+        // trackLastFrame: frame k-1's stereo map points -> calcOpticalFlowPyrLK into frame k -> edges
+        const int n_lk = (b->run_n + b->lk_step - 1) / b->lk_step;
+        int rc = yv_lk_build(b->lk, b->run_images, n_lk, b->run_stride, b->run_pitch * b->lk_step, s);
+        if (rc != YV_OK) return rc;
+        rc = yv_lk_track_batch(b->lk, b->lk_pairs, b->n_tracks, lkP, lkC, b->max_kp, b->lk_max_count, b->lk_eps,
+                               b->lk_min_eig, b->lk_next, b->lk_status, b->lk_err, s);
+        if (rc != YV_OK) return rc;
+        yavo::launch_lk_edges(b->n_tracks, lkX, b->lk_next, b->lk_status, lkQ, lkC, b->max_kp, eX, euv, eq, ec, s);
+        if (s != s_run) {
+            if (!b->ev_lk[lk_j]) YV_HIP(b->mem.event(&b->ev_lk[lk_j]));
+            YV_HIP(hipEventRecord(b->ev_lk[lk_j], s));
+            b->lk_ev_pending[lk_j] = true;
+        }
+    } else {
+        yavo::launch_track_build(b->tracks, b->n_tracks, b->pairs, b->keypoints, build_counts, b->match_dj,
+                                 b->match_lim, b->max_kp, b->track_K, b->T_right, eX, euv, eq, ec, s,
+                                 b->run_flags ? b->keep : nullptr);
+    }
+    if (b->overlap) YV_HIP(hipEventRecord(b->ev_edges[k], s));
+    if (s != s_run && b->lk_step == 0) {  // (the LK stage reads nothing the next run writes: no join)
+        YV_HIP(hipEventRecord(b->ev_built, s));
+        b->build_pending = true;
+    }
+    yv_batch::DeferredLM L;
+    L.active = true;
+    L.k = k;
+    L.run = timed ? run : -1;
+    L.priors = d_priors;
+    L.poses = d_poses;
+    L.ev = ev;
+    if (map) {
+        L.has_map = true;
+        L.first_frame = map->first_frame;
+        L.kf_every = map->kf_every;
+        L.max_kf = map->max_kf;
+        L.block = map->block;
+    }
+    b->tbuf = k;
+    if (b->overlap_mode >= 2) {
+        // launched by the next yv_batch_run after its detect (2) / describe (3) stage, or by a flush
+        b->deferred = L;
+        return check_launch();
+    }
+    const int rc = launch_lm(b, L, s);
+    if (rc != YV_OK) return rc;
+    return check_launch();
+}
+
+}  // namespace
+
+int yv_batch_set_track_overlap(yv_batch* b, int on) {
+    if (!b || on < 0 || on > 4) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
+    if (on && !b->side) {
+        // lowest priority: the LM fills the CUs the next batch's detect / describe / match leave idle
+        int least = 0, greatest = 0;
+        YV_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        YV_HIP(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, least));
+        b->mem.adopt(b->side);
+        for (int k = 0; k < kEdgeBufs; ++k) {
+            YV_HIP(b->mem.event(&b->ev_edges[k]));
+            YV_HIP(b->mem.event(&b->ev_lm[k]));
+        }
+        // the build stream at the default priority (the highest and the lowest measured the same)
+        YV_HIP(hipStreamCreateWithFlags(&b->bstream, hipStreamNonBlocking));
+        b->mem.adopt(b->bstream);
+        YV_HIP(b->mem.event(&b->ev_fin));
+        YV_HIP(b->mem.event(&b->ev_built));
+    }
+    if (!on && b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
+    if (!on) b->build_pending = false;
+    {
+        const char* e = std::getenv("YAVO_BUILD_ASYNC");
+        b->build_async = on != 0 && !(e && e[0] == '0');
+    }
+    if (!on && b->side) YV_HIP(hipStreamSynchronize(b->side));
+    b->overlap = on != 0;
+    b->overlap_mode = on;
+    return YV_OK;
+}
+
+int yv_batch_track_sync(yv_batch* b) {
+    if (!b) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
+    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
+    if (b->side) YV_HIP(hipStreamSynchronize(b->side));
+    return YV_OK;
+}
+
+int yv_batch_set_track_lk(yv_batch* b, int image_step, int win, int max_level, int max_count, double eps,
+                          double min_eig) {
+    if (!b || image_step < 0 || (image_step > 0 && (win < 3 || win > 22 || max_level < 0))) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
+    if (b->side) YV_HIP(hipStreamSynchronize(b->side));
+    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // an edge build in flight (as its siblings drain)
+    b->build_pending = false;
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    if (b->lk) {
+        yv_lk_destroy(b->lk);
+        b->lk = nullptr;
+    }
+    b->lk_step = image_step;
+    b->n_tracks = 0;  // tracks change meaning with the mode: set them again
+    if (image_step == 0) return YV_OK;
+    const int slots = (b->max_images + image_step - 1) / image_step;
+    const int rc = yv_lk_create(b->ctx, slots, b->H, b->W, win, max_level, &b->lk);
+    if (rc != YV_OK) {
+        b->lk_step = 0;
+        return rc;
+    }
+    b->lk_max_count = max_count;
+    b->lk_eps = eps;
+    b->lk_min_eig = min_eig;
+    return YV_OK;
+}
+
+}  // extern "C"

@@ -19,6 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "yavo_host.h"
 #include "yavo_internal.h"
 #include "yavo_cvsvd.h"
 #include "yavo_xlane.h"
@@ -1408,3 +1409,231 @@ void launch_recover_pose(const EssParams& P, const double* E, const float* pts1,
 }
 
 }  // namespace yavo
+
+// ------------------------------------------------------------------------------------------------
+// cv::findEssentialMat (RANSAC) + cv::recoverPose (yavo_geom.h)
+// ------------------------------------------------------------------------------------------------
+using namespace yavo;
+
+struct yv_essential {
+    yv_ctx* ctx = nullptr;
+    yavo::HipOwned mem;  // P's buffers
+    yavo::EssParams P;
+};
+
+extern "C" {
+
+int yv_essential_create(yv_ctx* ctx, int max_pairs, int max_points, int max_iters, yv_essential** out) {
+    if (!ctx || !out || max_pairs <= 0 || max_points < 5 || max_points > (1 << 20) || max_iters <= 0 ||
+        max_iters > 100000)
+        return YV_ERR_INVALID;
+    *out = nullptr;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    yv_essential* es = new (std::nothrow) yv_essential();
+    if (!es) return YV_ERR_INVALID;
+    es->ctx = ctx;
+    yavo::EssParams& P = es->P;
+    P.max_pairs = max_pairs;
+    P.max_points = max_points;
+    P.max_iters = max_iters;
+    P.chunk = yavo::ess_chunk_for(max_pairs);
+    const size_t np = (size_t)max_pairs;
+    if (es->mem.alloc(&P.m1, np * max_points * 2) != YV_OK || es->mem.alloc(&P.m2, np * max_points * 2) != YV_OK ||
+        es->mem.alloc(&P.idx, np * max_iters * 5) != YV_OK || es->mem.alloc(&P.models, np * P.chunk * 90) != YV_OK ||
+        es->mem.alloc(&P.nmod, np * P.chunk) != YV_OK || es->mem.alloc(&P.good, np * P.chunk * 10) != YV_OK ||
+        es->mem.alloc(&P.state, np * 8) != YV_OK || es->mem.alloc(&P.best, np * 9) != YV_OK ||
+        es->mem.alloc(&P.cand, np * 48) != YV_OK || es->mem.alloc(&P.cgood, np * 4) != YV_OK) {
+        delete es;
+        return YV_ERR_HIP;
+    }
+    if (P.chunk == yavo::kEssChunkWide) {
+        // cv::RNG((uint64)-1) states after 1 .. len draws: five per iteration plus room for the duplicate re-draws
+        const int len = 5 * max_iters + 2048;
+        std::vector<uint64_t> tab((size_t)len);
+        uint64_t st = ~0ull;
+        for (int k = 0; k < len; ++k) {
+            st = (uint64_t)(uint32_t)st * 4164903690ull + (st >> 32);  // cv::RNG::next (CV_RNG_COEFF)
+            tab[(size_t)k] = st;
+        }
+        if (es->mem.alloc(&P.rng_tab, (size_t)len) != YV_OK ||
+            hipMemcpy(P.rng_tab, tab.data(), sizeof(uint64_t) * (size_t)len, hipMemcpyHostToDevice) != hipSuccess) {
+            delete es;
+            return YV_ERR_HIP;
+        }
+        P.rng_len = len;
+    }
+    *out = es;
+    return YV_OK;
+}
+
+void yv_essential_destroy(yv_essential* es) {
+    if (!es) return;
+    (void)hipSetDevice(es->ctx->device);
+    (void)hipDeviceSynchronize();
+    delete es;
+}
+
+int yv_find_essential_batch(yv_essential* es, const float* d_pts1, const float* d_pts2, const int32_t* d_counts,
+                            int n_pairs, int pts_stride, double focal, double ppx, double ppy, double prob,
+                            double threshold, double* d_E, uint8_t* d_mask, int32_t* d_found, int32_t* d_stats,
+                            void* stream) {
+    if (!es || n_pairs < 0 || n_pairs > es->P.max_pairs || pts_stride < 0 || pts_stride > es->P.max_points ||
+        (n_pairs > 0 && (!d_pts1 || !d_pts2 || !d_counts || !d_E || !d_found)) || !(focal != 0.0) ||
+        !(prob > 0.0 && prob < 1.0))
+        return YV_ERR_INVALID;
+    if (n_pairs == 0) return YV_OK;
+    if (set_device(es->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : es->ctx->stream;
+    // a list holds at most pts_stride (<= max_points) points: longer counts are clipped on the device
+    yavo::EssRun r{focal, ppx, ppy, prob, threshold, es->P.max_iters};
+    yavo::launch_find_essential(es->P, r, d_pts1, d_pts2, d_counts, n_pairs, pts_stride, d_E, d_mask, d_found,
+                                d_stats, s);
+    return check_launch();
+}
+
+int yv_recover_pose_batch(yv_essential* es, const double* d_E, const float* d_pts1, const float* d_pts2,
+                          const int32_t* d_counts, int n_pairs, int pts_stride, const double K[9], double* d_R,
+                          double* d_t, int32_t* d_good, void* stream) {
+    if (!es || !K || n_pairs < 0 || n_pairs > es->P.max_pairs || pts_stride < 0 || pts_stride > es->P.max_points ||
+        (n_pairs > 0 && (!d_E || !d_pts1 || !d_pts2 || !d_counts || !d_R || !d_t)) || !(K[0] != 0.0) ||
+        !(K[4] != 0.0))
+        return YV_ERR_INVALID;
+    if (n_pairs == 0) return YV_OK;
+    if (set_device(es->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : es->ctx->stream;
+    yavo::Mat3 k;
+    for (int i = 0; i < 9; ++i) k.v[i] = K[i];
+    yavo::launch_recover_pose(es->P, d_E, d_pts1, d_pts2, d_counts, n_pairs, pts_stride, k, d_R, d_t, d_good, s);
+    return check_launch();
+}
+
+// Test entry point (tests/test_gpu_essential_degenerate.py; like yv_debug_xlane not part of the public headers): the
+// five-point solver alone, in the workspace's own form, on n_sets given subsets of five normalised correspondences
+// d_q1 / d_q2 [n_sets][5][2] -> d_models [n_sets][10][9] (zeros past a subset's count) and d_nmod [n_sets].  Overwrites
+// list 0 of the workspace.
+int yv_debug_ess_models(yv_essential* es, const double* d_q1, const double* d_q2, int n_sets, double* d_models,
+                        int32_t* d_nmod, void* stream) {
+    if (!es || !d_q1 || !d_q2 || !d_models || !d_nmod || n_sets <= 0 ||
+        n_sets > std::min(es->P.chunk, es->P.max_iters) || 5 * (int64_t)n_sets > es->P.max_points)
+        return YV_ERR_INVALID;
+    if (set_device(es->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : es->ctx->stream;
+    const int rc = yavo::launch_debug_ess_models(es->P, d_q1, d_q2, n_sets, d_models, d_nmod, s);
+    if (rc != 0) return rc == -1 ? YV_ERR_INVALID : YV_ERR_HIP;
+    return check_launch();
+}
+
+// the context's cached one-list essential workspace with room for `points` points and `iters` RANSAC iterations
+static int ctx_essential(yv_ctx* ctx, int points, int iters, yv_essential** out) {
+    yv_essential* es = ctx->ess_cache;
+    if (!es || es->P.max_points < points || es->P.max_iters < iters) {
+        if (es) yv_essential_destroy(es);
+        ctx->ess_cache = nullptr;
+        const int rc = yv_essential_create(ctx, 1, std::max(points, 2048), std::max(iters, 1000), &ctx->ess_cache);
+        if (rc != YV_OK) {
+            ctx->ess_cache = nullptr;
+            return rc;
+        }
+    }
+    *out = ctx->ess_cache;
+    return YV_OK;
+}
+
+int yv_find_essential(yv_ctx* ctx, const float* pts1, const float* pts2, int n, double focal, double ppx, double ppy,
+                      double prob, double threshold, double E[9], uint8_t* mask, int* found) {
+    if (!ctx || !E || !found || n < 0 || (n > 0 && (!pts1 || !pts2))) return YV_ERR_INVALID;
+    if (n > 65536) return YV_ERR_CAPACITY;
+    *found = 0;
+    for (int i = 0; i < 9; ++i) E[i] = 0.0;
+    if (n < 5) {
+        if (mask)
+            for (int i = 0; i < n; ++i) mask[i] = 0;
+        return YV_OK;
+    }
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    yv_essential* es = nullptr;
+    int rc = ctx_essential(ctx, n, 1000, &es);
+    if (rc != YV_OK) return rc;
+    hipStream_t s = ctx->stream;
+    Arena a{ctx};
+    float *d1, *d2;
+    double* dE;
+    uint8_t* dm;
+    int32_t *dcnt, *dfound;
+    // the points are read once (ess_prepare_kernel normalises them into the workspace), the outputs written once: all
+    // in the pinned mirror, no DMA
+    a.add_host(&d1, 2 * (size_t)n);
+    a.add_host(&d2, 2 * (size_t)n);
+    a.add_host(&dE, 9);
+    a.add_host(&dm, (size_t)n);
+    a.add_host(&dcnt, 1);
+    a.add_host(&dfound, 1);
+    if (a.commit() != YV_OK) return YV_ERR_HIP;
+    int st = YV_OK;
+    do {
+        a.in(d1, pts1, sizeof(float) * 2 * n);
+        a.in(d2, pts2, sizeof(float) * 2 * n);
+        a.in(dcnt, &n, sizeof(int32_t));
+        if (a.upload(s) != hipSuccess) {
+            st = YV_ERR_HIP;
+            break;
+        }
+        st = yv_find_essential_batch(es, d1, d2, dcnt, 1, n, focal, ppx, ppy, prob, threshold, dE, dm, dfound,
+                                     nullptr, nullptr);
+        if (st != YV_OK) break;
+        a.out(E, dE, sizeof(double) * 9);
+        a.out(found, dfound, sizeof(int32_t));
+        if (mask) a.out(mask, dm, (size_t)n);
+        if (a.fetch(s) != hipSuccess) st = YV_ERR_HIP;
+    } while (0);
+    return st;
+}
+
+int yv_recover_pose(yv_ctx* ctx, const double E[9], const float* pts1, const float* pts2, int n, const double K[9],
+                    double R[9], double t[3], int* good) {
+    if (!ctx || !E || !K || !R || !t || !good || n < 0 || (n > 0 && (!pts1 || !pts2))) return YV_ERR_INVALID;
+    if (n > 65536) return YV_ERR_CAPACITY;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    yv_essential* es = nullptr;
+    int rc = ctx_essential(ctx, std::max(n, 5), 1, &es);
+    if (rc != YV_OK) return rc;
+    hipStream_t s = ctx->stream;
+    Arena a{ctx};
+    float *d1, *d2;
+    double *dE, *dR, *dt;
+    int32_t *dcnt, *dgood;
+    // each point is read by its four candidate lanes once: all in the pinned mirror, no DMA
+    a.add_host(&d1, 2 * (size_t)std::max(n, 1));
+    a.add_host(&d2, 2 * (size_t)std::max(n, 1));
+    a.add_host(&dE, 9);
+    a.add_host(&dR, 9);
+    a.add_host(&dt, 3);
+    a.add_host(&dcnt, 1);
+    a.add_host(&dgood, 1);
+    if (a.commit() != YV_OK) return YV_ERR_HIP;
+    int st = YV_OK;
+    do {
+        if (n > 0) {
+            a.in(d1, pts1, sizeof(float) * 2 * n);
+            a.in(d2, pts2, sizeof(float) * 2 * n);
+        }
+        a.in(dE, E, sizeof(double) * 9);
+        a.in(dcnt, &n, sizeof(int32_t));
+        if (a.upload(s) != hipSuccess) {
+            st = YV_ERR_HIP;
+            break;
+        }
+        st = yv_recover_pose_batch(es, dE, d1, d2, dcnt, 1, std::max(n, 5), K, dR, dt, dgood, nullptr);
+        if (st != YV_OK) break;
+        a.out(R, dR, sizeof(double) * 9);
+        a.out(t, dt, sizeof(double) * 3);
+        a.out(good, dgood, sizeof(int32_t));
+        if (a.fetch(s) != hipSuccess) st = YV_ERR_HIP;
+    } while (0);
+    return st;
+}
+
+}  // extern "C"

@@ -1,4 +1,5 @@
-// yavo_internal.h -- launchers shared between the kernel translation unit and the C-ABI layer.
+// yavo_internal.h -- the launch interface: the kernels' launchers, constants and kernel-argument structs, shared between
+// the kernel translation units and the host side of the C ABI (yavo_host.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -277,14 +278,15 @@ struct EssRun {
 void launch_find_essential(const EssParams& P, const EssRun& r, const float* pts1, const float* pts2,
                            const int32_t* counts, int n_pairs, int pts_stride, double* E, uint8_t* mask,
                            int32_t* found, int32_t* stats, hipStream_t s);
-// test entry point behind yv_debug_ess_models (yavo_api.hip): the model kernel of the workspace's form on n_sets given
+// test entry point behind yv_debug_ess_models (below the kernels in yavo_essential.hip): the model kernel of the workspace's form on n_sets given
 // five-point subsets q1 / q2 [n_sets][5][2]; models [n_sets][10][9] (zeros past a subset's count), nmod [n_sets]
 int launch_debug_ess_models(const EssParams& P, const double* q1, const double* q2, int n_sets, double* models,
                             int32_t* nmod, hipStream_t s);
 struct Mat3 {
     double v[9];
 };
-// the context's device / stream for the host-side modules (yavo_io.hip); defined in yavo_api.hip
+// the context's device / stream for the host-side modules that do not see yv_ctx (yavo_io.hip); defined with the
+// context, beside yv_create in yavo_api.hip
 int ctx_device(struct ::yv_ctx* ctx);
 hipStream_t ctx_stream(struct ::yv_ctx* ctx);
 void launch_recover_pose(const EssParams& P, const double* E, const float* pts1, const float* pts2,

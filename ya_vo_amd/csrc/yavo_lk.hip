@@ -18,6 +18,7 @@
 #include <float.h>
 #include <stdint.h>
 
+#include "yavo_host.h"
 #include "yavo_internal.h"
 
 namespace yavo {
@@ -690,3 +691,233 @@ void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const
 }
 
 }  // namespace yavo
+
+// ------------------------------------------------------------------------------------------------
+// C ABI (include/yavo/yavo_geom.h): cv::calcOpticalFlowPyrLK
+// ------------------------------------------------------------------------------------------------
+using namespace yavo;
+
+struct yv_lk {
+    yv_ctx* ctx = nullptr;
+    int max_images = 0, H = 0, W = 0;
+    int built_images = 0;  // n_images of the last yv_lk_build
+    yavo::HipOwned mem;    // P.pyr, P.der and the event
+    hipEvent_t built = nullptr;  // recorded after the last yv_lk_build's pyramid, on the stream it ran on
+    yavo::LkParams P;
+};
+
+extern "C" {
+
+int yv_lk_create(yv_ctx* ctx, int max_images, int H, int W, int win, int max_level, yv_lk** out) {
+    if (!ctx || !out || max_images <= 0 || H < 1 || W < 1 || win < 3 || win > 22 || max_level < 0 ||
+        max_level >= yavo::kLkMaxLevels || (int64_t)H * W >= (1ll << 31))
+        return YV_ERR_INVALID;
+    *out = nullptr;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    yv_lk* lk = new (std::nothrow) yv_lk();
+    if (!lk) return YV_ERR_INVALID;
+    lk->ctx = ctx;
+    lk->max_images = max_images;
+    lk->H = H;
+    lk->W = W;
+    yavo::LkParams& P = lk->P;
+    P.win = win;
+    P.h[0] = H;
+    P.w[0] = W;
+    // buildOpticalFlowPyramid: stop when the next level would be <= winSize in either dimension
+    int levels = 0;
+    for (int l = 0; l < max_level; ++l) {
+        const int h = (P.h[l] + 1) / 2, w = (P.w[l] + 1) / 2;
+        if (w <= win || h <= win) break;
+        P.h[l + 1] = h;
+        P.w[l + 1] = w;
+        levels = l + 1;
+    }
+    P.levels = levels;
+    int64_t off = 0, doff = 0;
+    for (int l = 0; l <= levels; ++l) {
+        P.ps[l] = (P.w[l] + 63) & ~63;
+        P.ds[l] = (P.w[l] + 15) & ~15;
+        if (l >= 1) {
+            P.off[l] = off;
+            off += ((int64_t)P.h[l] * P.ps[l] + 255) & ~(int64_t)255;
+        }
+    }
+    doff = (int64_t)P.h[0] * P.ds[0] * 2;  // yv_lk_level's one-level derivative image (level 0 is the largest)
+    P.pyr_pitch = std::max<int64_t>(off, 256);
+    P.der_pitch = doff;
+    if (lk->mem.alloc(&P.pyr, (size_t)P.pyr_pitch * max_images) != YV_OK ||
+        lk->mem.alloc(&P.der, (size_t)P.der_pitch * sizeof(int16_t)) != YV_OK ||
+        lk->mem.event(&lk->built) != hipSuccess) {
+        delete lk;
+        return YV_ERR_HIP;
+    }
+    *out = lk;
+    return YV_OK;
+}
+
+void yv_lk_destroy(yv_lk* lk) {
+    if (!lk) return;
+    (void)hipSetDevice(lk->ctx->device);
+    (void)hipDeviceSynchronize();
+    delete lk;
+}
+
+int yv_lk_levels(const yv_lk* lk) { return lk ? lk->P.levels : YV_ERR_INVALID; }
+
+int yv_lk_level(yv_lk* lk, int image, int level, const uint8_t** d_img, int* img_stride, const int16_t** d_deriv,
+                int* deriv_stride, int* H, int* W) {
+    if (!lk || !lk->P.img0 || image < 0 || image >= lk->built_images || level < 0 || level > lk->P.levels ||
+        !d_img || !img_stride || !d_deriv || !deriv_stride || !H || !W)
+        return YV_ERR_INVALID;
+    if (set_device(lk->ctx) != YV_OK) return YV_ERR_HIP;
+    const yavo::LkParams& P = lk->P;
+    // the level's derivatives into the workspace's one-level image, complete on return.  The pyramid may have been
+    // built on a caller stream (the batch's LK mode passes its track stream): wait for that build first
+    if (hipStreamWaitEvent(lk->ctx->stream, lk->built, 0) != hipSuccess) return YV_ERR_HIP;
+    yavo::launch_lk_derivs(P, image, level, P.der, lk->ctx->stream);
+    if (check_launch() != YV_OK || hipStreamSynchronize(lk->ctx->stream) != hipSuccess) return YV_ERR_HIP;
+    if (level == 0) {
+        *d_img = P.img0 + image * P.pitch0;
+        *img_stride = P.stride0;
+    } else {
+        *d_img = P.pyr + image * P.pyr_pitch + P.off[level];
+        *img_stride = P.ps[level];
+    }
+    *d_deriv = P.der;
+    *deriv_stride = P.ds[level];
+    *H = P.h[level];
+    *W = P.w[level];
+    return YV_OK;
+}
+
+int yv_lk_build(yv_lk* lk, const uint8_t* d_images, int n_images, int stride, int64_t image_pitch, void* stream) {
+    if (!lk || !d_images || n_images <= 0 || n_images > lk->max_images || stride < lk->W ||
+        image_pitch < (int64_t)stride * (lk->H - 1) + lk->W)
+        return YV_ERR_INVALID;
+    if (set_device(lk->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : lk->ctx->stream;
+    lk->P.img0 = d_images;
+    lk->P.stride0 = stride;
+    lk->P.pitch0 = image_pitch;
+    lk->built_images = n_images;
+    yavo::launch_lk_pyramid(lk->P, n_images, s);
+    if (check_launch() != YV_OK || hipEventRecord(lk->built, s) != hipSuccess) return YV_ERR_HIP;
+    return YV_OK;
+}
+
+int yv_lk_track_batch(yv_lk* lk, const int32_t* d_pairs, int n_pairs, const float* d_pts, const int32_t* d_counts,
+                      int pts_stride, int max_count, double eps, double min_eig, float* d_next, uint8_t* d_status,
+                      float* d_err, void* stream) {
+    if (!lk || !lk->P.img0 || n_pairs < 0 || pts_stride < 0 ||
+        (n_pairs > 0 && (!d_pairs || !d_pts || !d_counts || !d_next || !d_status || !d_err)))
+        return YV_ERR_INVALID;
+    if (n_pairs == 0 || pts_stride == 0) return YV_OK;
+    if (set_device(lk->ctx) != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : lk->ctx->stream;
+    yavo::LkParams P = lk->P;
+    // TermCriteria handling of SparsePyrLKOpticalFlowImpl: maxCount clipped to [0, 100], eps to [0, 10], squared
+    P.max_count = std::min(std::max(max_count, 0), 100);
+    const double e = std::min(std::max(eps, 0.), 10.);
+    P.eps2 = e * e;
+    P.min_eig = min_eig;
+    yavo::launch_lk_track(P, d_pairs, n_pairs, d_pts, d_counts, pts_stride, pts_stride, d_next, d_status, d_err, s);
+    return check_launch();
+}
+
+int yv_calc_optical_flow_pyr_lk(yv_ctx* ctx, const uint8_t* prev, const uint8_t* next, int H, int W, int stride,
+                                const float* prev_pts, int n, int win, int max_level, int max_count, double eps,
+                                double min_eig, float* next_pts, uint8_t* status, float* err) {
+    if (!ctx || !prev || !next || n < 0 || (n > 0 && (!prev_pts || !next_pts || !status || !err)) || stride < W)
+        return YV_ERR_INVALID;
+    if (n > 65536) return YV_ERR_CAPACITY;
+    if (n == 0) return YV_OK;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    const int64_t pitch = (int64_t)H * W;
+    const int key[4] = {H, W, win, max_level};
+    if (!ctx->lk_cache || !std::equal(key, key + 4, ctx->lk_key)) {
+        if (ctx->lk_cache) yv_lk_destroy(ctx->lk_cache);
+        ctx->lk_cache = nullptr;
+        ctx->mem.release(ctx->lk_img_d, ctx->lk_img_h);
+        ctx->lk_last = -1;
+        int rc = yv_lk_create(ctx, 2, H, W, win, max_level, &ctx->lk_cache);
+        if (rc != YV_OK) {
+            ctx->lk_cache = nullptr;
+            return rc;
+        }
+        if (ctx->mem.alloc(&ctx->lk_img_d, (size_t)(2 * pitch + 64)) != YV_OK ||
+            ctx->mem.alloc_host(&ctx->lk_img_h, (size_t)(2 * pitch)) != YV_OK) {
+            yv_lk_destroy(ctx->lk_cache);
+            ctx->lk_cache = nullptr;
+            ctx->mem.release(ctx->lk_img_d, ctx->lk_img_h);
+            return YV_ERR_HIP;
+        }
+        std::copy(key, key + 4, ctx->lk_key);
+    }
+    yv_lk* lk = ctx->lk_cache;
+    hipStream_t s = ctx->stream;
+    // the image slots: prev is found in the slot the previous call left its next image in when the bytes are equal
+    // (its pyramid is still in that slot too); otherwise both images go up and both pyramids are built
+    auto same_image = [&](const uint8_t* img, const uint8_t* slot) {
+        if (stride == W) return std::memcmp(img, slot, (size_t)pitch) == 0;
+        for (int r = 0; r < H; ++r)
+            if (std::memcmp(img + (size_t)r * stride, slot + (size_t)r * W, (size_t)W) != 0) return false;
+        return true;
+    };
+    auto put_image = [&](const uint8_t* img, int slot) -> hipError_t {
+        uint8_t* h = ctx->lk_img_h + slot * pitch;
+        if (stride == W) std::memcpy(h, img, (size_t)pitch);
+        else
+            for (int r = 0; r < H; ++r) std::memcpy(h + (size_t)r * W, img + (size_t)r * stride, (size_t)W);
+        return hipMemcpyAsync(ctx->lk_img_d + slot * pitch, h, (size_t)pitch, hipMemcpyHostToDevice, s);
+    };
+    // next goes to the slot the previous call's next is not in; its upload runs while prev is compared with that one
+    const int ns = ctx->lk_last >= 0 ? 1 - ctx->lk_last : 1, ps = 1 - ns;
+    const bool had = ctx->lk_last >= 0;
+    ctx->lk_last = -1;  // until this call has completed
+    if (put_image(next, ns) != hipSuccess) return YV_ERR_HIP;
+    const bool reuse = had && same_image(prev, ctx->lk_img_h + ps * pitch);
+    Arena a{ctx};
+    float *dpts, *dnext, *derr;
+    int32_t *dpair, *dcnt;
+    uint8_t* dst;
+    // points read once, outputs written once: in the pinned mirror (the images have their own slots)
+    a.add_host(&dpts, 2 * (size_t)n);
+    a.add_host(&dnext, 2 * (size_t)n);
+    a.add_host(&derr, (size_t)n);
+    a.add_host(&dpair, 2);
+    a.add_host(&dcnt, 1);
+    a.add_host(&dst, (size_t)n);
+    if (a.commit() != YV_OK) return YV_ERR_HIP;
+    const int32_t pair[3] = {ps, ns, n};
+    a.in(dpts, prev_pts, sizeof(float) * 2 * n);
+    a.in(dpair, pair, 2 * sizeof(int32_t));
+    a.in(dcnt, pair + 2, sizeof(int32_t));
+    if ((!reuse && put_image(prev, ps) != hipSuccess) || a.upload(s) != hipSuccess) return YV_ERR_HIP;
+    yavo::LkParams& P = lk->P;
+    P.img0 = ctx->lk_img_d;
+    P.stride0 = W;
+    P.pitch0 = pitch;
+    lk->built_images = 2;
+    if (reuse) {  // only the new image's pyramid (slot ns)
+        yavo::LkParams P1 = P;
+        P1.img0 = ctx->lk_img_d + ns * pitch;
+        P1.pyr = P.pyr + ns * P.pyr_pitch;
+        yavo::launch_lk_pyramid(P1, 1, s);
+    } else {
+        yavo::launch_lk_pyramid(P, 2, s);
+    }
+    if (check_launch() != YV_OK || hipEventRecord(lk->built, s) != hipSuccess) return YV_ERR_HIP;
+    int status_rc = yv_lk_track_batch(lk, dpair, 1, dpts, dcnt, n, max_count, eps, min_eig, dnext, dst, derr, nullptr);
+    if (status_rc != YV_OK) return status_rc;
+    a.out(next_pts, dnext, sizeof(float) * 2 * n);
+    a.out(status, dst, (size_t)n);
+    a.out(err, derr, sizeof(float) * n);
+    if (a.fetch(s) != hipSuccess) return YV_ERR_HIP;
+    ctx->lk_last = ns;
+    return YV_OK;
+}
+
+}  // extern "C"
