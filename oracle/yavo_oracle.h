@@ -228,8 +228,16 @@ int or_ba_lm(double* poses, int P, int n_fixed, double* X, int L, const int32_t*
  * (yavo_oracle_ba.c header): the order the trajectory tolerance is measured against */
 int or_ba_lm_mode(double* poses, int P, int n_fixed, double* X, int L, const int32_t* ep, const int32_t* el,
                   const double* meas, int E, const double* K, int max_iters, double* chi2_log, int mode);
+/* diagnostics: when or_ba_dump_iter >= 0, the first damping trial of that iteration copies its buffers into
+ * or_ba_dump[which] where non-NULL (the order of yv_ba_debug_read; S before factorisation) */
 extern int or_ba_dump_iter;
 extern double* or_ba_dump[16];
+/* diagnostics: when non-NULL, iteration it < or_ba_trial_cap records [OR_BA_TRIAL * it] = {trials run (q), trials
+ * whose LDLT was not positive, trials whose rho was NaN, why the run stopped after it (0: it went on; bits 1: q == 10,
+ * 2: rho == 0, 4: lambda non-finite)} */
+#define OR_BA_TRIAL 4
+extern int* or_ba_trial_log;
+extern int or_ba_trial_cap;
 
 /* ---- shared map blocks (include/yavo/yavo_map.h; src/Map.cc:9-40) -- yavo_oracle_map.c ---- */
 int64_t or_map_block_bytes(int max_kf, int lm_stride);

@@ -295,6 +295,13 @@ static void ba_dump(int which, const double* src, size_t n) {
     if (or_ba_dump[which]) memcpy(or_ba_dump[which], src, sizeof(double) * n);
 }
 
+/* diagnostics (tests only): when or_ba_trial_log is non-NULL, iteration it < or_ba_trial_cap of or_ba_lm_mode
+ * records OR_BA_TRIAL ints at [OR_BA_TRIAL * it]: {q = the trials run, the trials whose LDLT was not positive, the
+ * trials whose rho was NaN, why the run stopped after it (0: it did not; bits 1: q == 10, 2: rho == 0, 4: lambda
+ * non-finite)}.  Counters only: no arithmetic of the solve reads them. */
+int* or_ba_trial_log = NULL;
+int or_ba_trial_cap = 0;
+
 /* or_ba_lm: g2o LM with BlockSolver_6_3 (see the header); poses [P][7] (T_cw, SE3d::data()), X [L][3] in / out.
  * chi2_log [max_iters + 1] (may be NULL): chi2 before iteration 0 and after each iteration.  Returns the
  * iterations run (an iteration that fails 10 trials ends the run, as g2o's Terminate). */
@@ -418,6 +425,7 @@ int or_ba_lm_mode(double* poses, int P, int n_fixed, double* X, int L, const int
         }
         double rho = 0;
         int q = 0;
+        int not_positive = 0, nan_rho = 0;  /* the trial log's counters */
         do {
             memcpy(bak_p, poses, sizeof(double) * 7 * (size_t)P);
             memcpy(bak_X, X, sizeof(double) * 3 * (size_t)L);
@@ -555,6 +563,7 @@ int or_ba_lm_mode(double* poses, int P, int n_fixed, double* X, int L, const int
             }
             double tempChi = g2o ? ba_chi2_g2o(&s, poses, X) : ba_chi2(&s, poses, X, lsum);
             if (!ok2) tempChi = DBL_MAX;
+            not_positive += !ok2;
             rho = currentChi - tempChi;
             /* computeScale over the variables: the free poses' items in tree256 order (leaf t = items j = t mod 256
              * ascending from 0.0), plus the landmarks' in the landmark-block order of 0.0 + their three items */
@@ -577,6 +586,7 @@ int or_ba_lm_mode(double* poses, int P, int n_fixed, double* X, int L, const int
             }
             scale += 1e-3;
             rho /= scale;
+            nan_rho += isnan(rho) ? 1 : 0;
             if (rho > 0 && isfinite(tempChi)) {
                 double alpha = 1. - or_lm_cube(2 * rho - 1);  /* pow(2 rho - 1, 3): correctly rounded, or libm */
                 alpha = fmin(alpha, 2. / 3.);
@@ -593,6 +603,13 @@ int or_ba_lm_mode(double* poses, int P, int n_fixed, double* X, int L, const int
             q++;
         } while (rho < 0 && q < 10);
         if (chi2_log) chi2_log[it + 1] = currentChi;
+        if (or_ba_trial_log && it < or_ba_trial_cap) {
+            int* tl = or_ba_trial_log + OR_BA_TRIAL * it;
+            tl[0] = q;
+            tl[1] = not_positive;
+            tl[2] = nan_rho;
+            tl[3] = (q == 10 ? 1 : 0) | (rho == 0 ? 2 : 0) | (!isfinite(lambda) ? 4 : 0);
+        }
         if (q == 10 || rho == 0 || !isfinite(lambda)) {
             ++it;
             break;

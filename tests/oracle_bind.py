@@ -500,6 +500,46 @@ class Oracle:
                                     _p(K), max_iters, _p(log), int(mode))
         return T, Xo, it, log[:it + 1]
 
+    # yv_ba_debug_read's buffer order (or_ba_dump[which]); H_pl, W and Dinv exist in the oracle only
+    BA_STAGES = ("err", "J_pose", "J_point", "H_pl", "W", "H_pp", "b_p", "H_ll", "b_l", "Dinv", "S", "b_schur", "x_p",
+                 "x_l", "poses", "X")
+
+    def ba_lm_trials(self, poses, n_fixed, X, ep, el, meas, K, max_iters=10, mode=0):
+        """ba_lm with the trial log (or_ba_trial_log) -> (poses, X, iterations, chi2 log, trials [iterations, 4]); a
+        trials row is (q = trials run, trials whose LDLT was not positive, trials with a NaN rho, the stop reason: 0
+        none, bits 1 q == 10, 2 rho == 0, 4 non-finite lambda)."""
+        trials = np.zeros((max(max_iters, 1), 4), np.int32)
+        log_p = ctypes.c_void_p.in_dll(self.lib, "or_ba_trial_log")
+        cap = ctypes.c_int.in_dll(self.lib, "or_ba_trial_cap")
+        log_p.value, cap.value = trials.ctypes.data, max_iters
+        try:
+            T, Xo, it, log = self.ba_lm(poses, n_fixed, X, ep, el, meas, K, max_iters, mode)
+        finally:
+            log_p.value, cap.value = None, 0
+        return T, Xo, it, log, trials[:it]
+
+    def ba_dump(self, poses, n_fixed, X, ep, el, meas, K, dump_iter=0, mode=0):
+        """The buffers of iteration dump_iter's first damping trial (or_ba_dump; S before its factorisation) as a
+        dict by BA_STAGES name; the oracle runs dump_iter + 1 iterations. The solve never writes the H_pp / b_p
+        rows of fixed poses: compare the free poses' rows only."""
+        P, L, E = len(poses), len(X), len(ep)
+        ns = 6 * (P - n_fixed)
+        sizes = (2 * E, 12 * E, 6 * E, 18 * E, 18 * E, 36 * P, 6 * P, 9 * L, 3 * L, 9 * L, ns * ns, ns, ns, 3 * L,
+                 7 * P, 3 * L)
+        bufs = [np.full(max(n, 1), np.nan) for n in sizes]
+        slots = (ctypes.c_void_p * 16).in_dll(self.lib, "or_ba_dump")
+        which = ctypes.c_int.in_dll(self.lib, "or_ba_dump_iter")
+        for i, b in enumerate(bufs):
+            slots[i] = b.ctypes.data
+        which.value = dump_iter
+        try:
+            self.ba_lm(poses, n_fixed, X, ep, el, meas, K, dump_iter + 1, mode)
+        finally:
+            which.value = -1
+            for i in range(16):
+                slots[i] = None
+        return {name: b[:n] for name, b, n in zip(self.BA_STAGES, bufs, sizes)}
+
     # ---- shared map blocks (include/yavo/yavo_map.h) ----
     def map_block_bytes(self, max_kf, lm_stride):
         return int(self.lib.or_map_block_bytes(max_kf, lm_stride))

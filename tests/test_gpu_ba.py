@@ -88,6 +88,15 @@ def test_ba_rejects_bad_graph(ctx):
         ba.set_problem(5, 1, 10, ep, el, np.zeros((2, 2)), scene.K_KITTI)  # more poses than the workspace
     with pytest.raises(yv.YavoError):
         ba.set_problem(4, 5, 10, np.array([0, 1], np.int32), el, np.zeros((2, 2)), scene.K_KITTI)
+    ok = np.array([0, 1], np.int32)
+    ba.set_problem(4, 1, 10, ok, el, np.zeros((2, 2)), scene.K_KITTI)  # the graph itself is accepted
+    for bad in (np.nan, np.inf):
+        K = scene.K_KITTI.copy()
+        K[1, 2] = bad  # a non-finite K entry
+        with pytest.raises(yv.YavoError):
+            ba.set_problem(4, 1, 10, ok, el, np.zeros((2, 2)), K)
+    with pytest.raises(yv.YavoError):
+        ba.set_problem(4, 1, 10, ok, np.array([0, -1], np.int32), np.zeros((2, 2)), scene.K_KITTI)  # landmark -1
 
 
 @pytest.mark.timeout(300)

@@ -862,6 +862,14 @@ class BundleAdjuster:
         """Suspended trial loops the device LM resumed from the host so far (yv_ba_debug_resumes)."""
         return int(self.lib.yv_ba_debug_resumes(self.handle))
 
+    def debug_read(self, which: int, count: int) -> np.ndarray:
+        """The first `count` doubles of a workspace buffer as the last solve left it (yv_ba_debug_read). which: 0 err,
+        1 J_pose, 2 J_point, 5 H_pp, 6 b_p, 7 H_ll, 8 b_l, 10 S, 11 b_schur, 12 x_p, 13 x_l, 14 poses, 15 X, 16 the
+        scalars; 3, 4 and 9 (H_pl, W, Dinv) are no longer stored and raise YavoError."""
+        out = np.zeros(int(count))
+        _check(self.lib.yv_ba_debug_read(self.handle, int(which), _ptr(out), int(count)), "yv_ba_debug_read")
+        return out
+
     def set_problem(self, n_poses: int, n_fixed: int, n_landmarks: int, edge_pose, edge_landmark, meas, K) -> None:
         self._ep = np.ascontiguousarray(edge_pose, np.int32).reshape(-1)
         self._el = np.ascontiguousarray(edge_landmark, np.int32).reshape(-1)
