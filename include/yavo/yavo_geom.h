@@ -84,9 +84,15 @@ int yv_f_ransac_batch(struct yv_ctx* ctx, const yv_match* d_matches, int64_t lis
  * Restates OpenCV's pyramidal LK (flags 0: no initial flow) -- pyrDown pyramid (levels stop when the next one
  * would be <= win), Scharr derivatives, 14-bit bilinear windows, minEig test, Newton steps with the eps^2 and
  * oscillation tests, the level-0 error.  Points are cv::Point2f (x = column, y = row).  Window sums use the
- * GPU order of oracle/yavo_oracle_lk.c (sum_mode 1). */
+ * GPU order of oracle/yavo_oracle_lk.c (sum_mode 1).
+ * Any float is a valid point coordinate.  A point with a coordinate that is NaN, infinite or beyond +-2^31 is
+ * rejected like one whose window lies outside the image, as OpenCV's x86 build does (cvFloor gives INT_MIN there):
+ * status 0, err 0, next point = the input (NaN stays NaN), and nothing is read at it.
+ * Any H, W >= 1 is a valid image size, also below the window: image pixels are REFLECT_101 at any distance
+ * (cv::borderInterpolate's period 2 len - 2). */
 typedef struct yv_lk yv_lk;
-/* Workspace for up to max_images H x W images: pyramids and derivatives.  win <= 22, max_level <= 7. */
+/* Workspace for up to max_images H x W images: pyramids and derivatives.  3 <= win <= 22, 0 <= max_level <= 7;
+ * anything else is YV_ERR_INVALID. */
 int yv_lk_create(struct yv_ctx* ctx, int max_images, int H, int W, int win, int max_level, yv_lk** out);
 void yv_lk_destroy(yv_lk* lk);
 /* Levels actually used (buildOpticalFlowPyramid's return value). */

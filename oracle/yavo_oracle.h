@@ -186,6 +186,29 @@ void or_scharr(const uint8_t* src, int H, int W, int sstride, int16_t* d);
 int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_pts, int n, int win,
               int max_level, int max_count, double eps, double min_eig, float* next_pts, uint8_t* status,
               float* err, int sum_mode);
+/* The same with a trace [n][OR_LK_TRACE_LEVELS][2] (NULL: none): per point and pyramid level {the exit taken, Newton
+ * steps taken}; levels above the top level used stay {OR_LK_NOT_RUN, 0}.  The exits are those of one point at one
+ * level, in the order they are met: the window of the scaled point lies outside the level; minEig below the threshold;
+ * minEig passes but the determinant D < FLT_EPSILON; the moving window left the level before step j (j = the steps
+ * taken); the step's squared length <= eps^2; the oscillation stop (half of the last step taken back); max_count steps
+ * taken (also max_count 0); and, at level 0 only and replacing one of the last three, the window of the final point
+ * lies outside (status 0, no error).  A point that is not finite or beyond +-2^31 takes the first exit. */
+enum {
+    OR_LK_NOT_RUN = 0,
+    OR_LK_WINDOW_OUTSIDE = 1,
+    OR_LK_MIN_EIG = 2,
+    OR_LK_DET = 3,
+    OR_LK_LEFT_IMAGE = 4,
+    OR_LK_EPS = 5,
+    OR_LK_OSCILLATION = 6,
+    OR_LK_MAX_COUNT = 7,
+    OR_LK_ERR_OUTSIDE = 8
+};
+#define OR_LK_TRACE_LEVELS 8
+#define OR_LK_TRACE_POINT (2 * OR_LK_TRACE_LEVELS)
+int or_lk_pyr_ex(const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_pts, int n, int win,
+                 int max_level, int max_count, double eps, double min_eig, float* next_pts, uint8_t* status,
+                 float* err, int sum_mode, int32_t* trace);
 
 /* ---- cv::findEssentialMat (RANSAC) + cv::recoverPose (yavo_oracle_essential.c) ---- */
 /* getSubset draws of RANSACPointSetRegistrator::run (cv::RNG((uint64)-1)): idx [iters][5] */

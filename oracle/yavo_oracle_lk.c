@@ -18,11 +18,22 @@
  * partials are then combined by the butterfly q[l] = q[l] + q[l ^ off], off = 8, 4, 2, 1, whose lane-0 value
  * is the tree p[l] += p[l + off]).  The
  * reference's x86 OpenCV build runs a 4-lane SIMD path for x < 8 of each row, another float order: parity
- * with the reference binary is unpinned (no fixture holds LK outputs).
+ * with the reference binary is unpinned (no fixture holds LK outputs).  What is pinned: pyrDown and Scharr by numpy
+ * restatements, and one Newton step (weights, window integers, A, b, minEig, the step and the accept / reject
+ * decision) by the float64 statement of tests/lk_reference.py (tests/test_oracle_lk.py).
+ *
+ * Float -> int: OpenCV's cvFloor(v) on the reference's x86 build is cvtss2si of v (minus one where that rounded up),
+ * which gives INT_MIN for a NaN, an infinity and every |v| >= 2^31; (int)floorf(v) is undefined in C for those.
+ * lk_floor below is defined for every float and returns INT_MIN there, so the range check that follows each of its
+ * three uses rejects such a point (status 0, err 0, next = the scaled input) before anything is read at it.
+ *
+ * or_lk_pyr_ex also records which exit each point took at each level (OR_LK_* in yavo_oracle.h); or_lk_pyr is that
+ * call without a trace.
  */
 #include "yavo_oracle.h"
 
 #include <float.h>
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -91,6 +102,12 @@ static int der_at(const lk_level* L, int y, int x, int c) {
     return L->der[(y * L->W + x) * 2 + c];
 }
 
+/* floor(v) as an int; INT_MIN where it does not fit (non-finite v, |v| >= 2^31), as cvFloor gives on x86 */
+static int lk_floor(float v) {
+    const float f = floorf(v);
+    return fabsf(f) < 2147483648.f ? (int)f : INT_MIN;
+}
+
 #define LK_W_BITS 14
 #define LK_DESCALE(x, n) (((x) + (1 << ((n)-1))) >> (n))
 
@@ -126,7 +143,11 @@ static void lk_weights(float a, float b, int* iw) {
 /* One point at one level (LKTrackerInvoker::operator() body). */
 static void lk_point(const lk_level* I, const lk_level* J, int level, int max_level, int win, int max_count,
                      double eps2, double min_eig_thr, const float* prev_pt, float* next_pt, uint8_t* status,
-                     float* err, int sum_mode) {
+                     float* err, int sum_mode, int32_t* tr) {
+    int32_t tr_none[2];
+    if (!tr) tr = tr_none;
+    tr[0] = OR_LK_WINDOW_OUTSIDE;
+    tr[1] = 0;
     const float halfw = (float)((win - 1) * 0.5f);
     const float scale = (float)(1. / (1 << level));
     float px = prev_pt[0] * scale, py = prev_pt[1] * scale;
@@ -142,7 +163,7 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
     next_pt[1] = ny;
     px -= halfw;
     py -= halfw;
-    const int ipx = (int)floorf(px), ipy = (int)floorf(py);
+    const int ipx = lk_floor(px), ipy = lk_floor(py);
     if (ipx < -win || ipx >= I->W || ipy < -win || ipy >= I->H) {
         if (level == 0) {
             *status = 0;
@@ -182,6 +203,7 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
     float D = A11 * A22 - A12 * A12;
     const float minEig = (A22 + A11 - sqrtf((A11 - A22) * (A11 - A22) + 4.f * A12 * A12)) / (float)(2 * win * win);
     if (minEig < min_eig_thr || D < FLT_EPSILON) {
+        tr[0] = minEig < min_eig_thr ? OR_LK_MIN_EIG : OR_LK_DET;
         if (level == 0) *status = 0;
         free(Iw);
         free(t11);
@@ -192,9 +214,11 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
     ny -= halfw;
     float pdx = 0.f, pdy = 0.f;
     float* tb = t11;  /* reuse: tb1 = t11, tb2 = t12 */
+    tr[0] = OR_LK_MAX_COUNT;
     for (int j = 0; j < max_count; ++j) {
-        const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+        const int inx = lk_floor(nx), iny = lk_floor(ny);
         if (inx < -win || inx >= J->W || iny < -win || iny >= J->H) {
+            tr[0] = OR_LK_LEFT_IMAGE;
             if (level == 0) *status = 0;
             break;
         }
@@ -216,8 +240,13 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
         ny += dy;
         next_pt[0] = nx + halfw;
         next_pt[1] = ny + halfw;
-        if ((double)dx * dx + (double)dy * dy <= eps2) break;
+        tr[1] = j + 1;
+        if ((double)dx * dx + (double)dy * dy <= eps2) {
+            tr[0] = OR_LK_EPS;
+            break;
+        }
         if (j > 0 && fabsf(dx + pdx) < 0.01 && fabsf(dy + pdy) < 0.01) {
+            tr[0] = OR_LK_OSCILLATION;
             next_pt[0] -= dx * 0.5f;
             next_pt[1] -= dy * 0.5f;
             break;
@@ -227,8 +256,9 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
     }
     if (*status && level == 0) {
         const float ex = next_pt[0] - halfw, ey = next_pt[1] - halfw;
-        const int inx = (int)floorf(ex), iny = (int)floorf(ey);
+        const int inx = lk_floor(ex), iny = lk_floor(ey);
         if (inx < -win || inx >= J->W || iny < -win || iny >= J->H) {
+            tr[0] = OR_LK_ERR_OUTSIDE;
             *status = 0;
         } else {
             lk_weights(ex - (float)inx, ey - (float)iny, iw);
@@ -250,9 +280,9 @@ static void lk_point(const lk_level* I, const lk_level* J, int level, int max_le
 /* cv::calcOpticalFlowPyrLK(prev, next, prevPts, nextPts, status, err, Size(win, win), max_level,
  * TermCriteria(COUNT+EPS, max_count, eps), 0, min_eig) on u8 images [H][W].  pts are (x = column,
  * y = row) as cv::Point2f.  Returns the number of pyramid levels - 1 actually used. */
-int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_pts, int n, int win,
-              int max_level, int max_count, double eps, double min_eig, float* next_pts, uint8_t* status,
-              float* err, int sum_mode) {
+int or_lk_pyr_ex(const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_pts, int n, int win,
+                 int max_level, int max_count, double eps, double min_eig, float* next_pts, uint8_t* status,
+                 float* err, int sum_mode, int32_t* trace) {
     /* pyramid sizes (buildOpticalFlowPyramid: stop when the next level would be <= winSize) */
     int Hs[16], Ws[16], levels = 0;
     Hs[0] = H;
@@ -278,6 +308,7 @@ int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const floa
         status[i] = 1;
         err[i] = 0.f;
     }
+    if (trace) memset(trace, 0, sizeof(int32_t) * OR_LK_TRACE_POINT * (size_t)n);
     /* TermCriteria: eps clipped to [0, 10] and squared; maxCount clipped to [0, 100] */
     double e = eps < 0 ? 0 : (eps > 10 ? 10 : eps);
     const double eps2 = e * e;
@@ -288,7 +319,7 @@ int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const floa
         lk_level I = {Hs[l], Ws[l], pp[l], der}, J = {Hs[l], Ws[l], np[l], NULL};
         for (int i = 0; i < n; ++i)
             lk_point(&I, &J, l, levels, win, mc, eps2, min_eig, prev_pts + 2 * i, next_pts + 2 * i, status + i,
-                     err + i, sum_mode);
+                     err + i, sum_mode, trace && l < OR_LK_TRACE_LEVELS ? trace + OR_LK_TRACE_POINT * i + 2 * l : NULL);
         free(der);
     }
     for (int l = 1; l <= levels; ++l) {
@@ -296,4 +327,11 @@ int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const floa
         free(np[l]);
     }
     return levels;
+}
+
+int or_lk_pyr(const uint8_t* prev, const uint8_t* next, int H, int W, const float* prev_pts, int n, int win,
+              int max_level, int max_count, double eps, double min_eig, float* next_pts, uint8_t* status,
+              float* err, int sum_mode) {
+    return or_lk_pyr_ex(prev, next, H, W, prev_pts, n, win, max_level, max_count, eps, min_eig, next_pts, status,
+                        err, sum_mode, NULL);
 }

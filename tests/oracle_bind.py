@@ -74,6 +74,8 @@ class Oracle:
             "or_scharr": (None, [_P, _I, _I, _I, _P]),
             "or_lk_pyr": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P,
                                _I]),
+            "or_lk_pyr_ex": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _P, _P,
+                                  _I, _P]),
             "or_em_subsets": (None, [_I, _I, _P]),
             "or_em_coeff_mat": (None, [_P, _P]),
             "or_em_det_poly": (None, [_P, _P]),
@@ -402,8 +404,15 @@ class Oracle:
         self.lib.or_scharr(_p(img), H, W, W, _p(out))
         return out
 
-    def lk(self, prev, nxt, pts, win=11, max_level=3, max_count=30, eps=0.01, min_eig=0.001, sum_mode=0):
-        """-> (next_pts [n, 2] (x = col, y = row), status [n] bool, err [n], top level used)."""
+    # the exits of one point at one pyramid level (OR_LK_* in oracle/yavo_oracle.h)
+    LK_NOT_RUN, LK_WINDOW_OUTSIDE, LK_MIN_EIG, LK_DET, LK_LEFT_IMAGE, LK_EPS, LK_OSCILLATION, LK_MAX_COUNT, \
+        LK_ERR_OUTSIDE = range(9)
+    LK_TRACE_LEVELS = 8
+
+    def lk(self, prev, nxt, pts, win=11, max_level=3, max_count=30, eps=0.01, min_eig=0.001, sum_mode=0, trace=False):
+        """-> (next_pts [n, 2] (x = col, y = row), status [n] bool, err [n], top level used); with trace=True a fifth
+        item, the dict {exit [n, 8] (LK_* per pyramid level, LK_NOT_RUN above the top level), steps [n, 8] (Newton
+        steps taken)} of or_lk_pyr_ex."""
         prev = np.ascontiguousarray(prev, np.uint8)
         nxt = np.ascontiguousarray(nxt, np.uint8)
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
@@ -411,9 +420,16 @@ class Oracle:
         nextp = np.zeros_like(pts)
         status = np.zeros(max(len(pts), 1), np.uint8)
         err = np.zeros(max(len(pts), 1), np.float32)
-        lv = self.lib.or_lk_pyr(_p(prev), _p(nxt), H, W, _p(pts), len(pts), win, max_level, max_count, eps, min_eig,
-                                _p(nextp), _p(status), _p(err), sum_mode)
-        return nextp, status[:len(pts)].astype(bool), err[:len(pts)], lv
+        args = (_p(prev), _p(nxt), H, W, _p(pts), len(pts), win, max_level, max_count, eps, min_eig, _p(nextp),
+                _p(status), _p(err), sum_mode)
+        if not trace:
+            lv = self.lib.or_lk_pyr(*args)
+            return nextp, status[:len(pts)].astype(bool), err[:len(pts)], lv
+        tr = np.zeros((max(len(pts), 1), self.LK_TRACE_LEVELS, 2), np.int32)
+        lv = self.lib.or_lk_pyr_ex(*args, _p(tr))
+        tr = tr[:len(pts)]
+        return nextp, status[:len(pts)].astype(bool), err[:len(pts)], lv, dict(exit=tr[:, :, 0].copy(),
+                                                                                  steps=tr[:, :, 1].copy())
 
     # ---- findEssentialMat / recoverPose ----
     def em_subsets(self, count, iters):

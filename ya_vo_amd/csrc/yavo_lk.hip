@@ -16,6 +16,7 @@
 // Built with -ffp-contract=off like the rest: each float op rounds as the oracle's.
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "yavo_host.h"
@@ -25,7 +26,8 @@ namespace yavo {
 namespace lk {
 
 __device__ __forceinline__ int refl(int p, int len) {
-    // cv::borderInterpolate(BORDER_REFLECT_101) for |p| < 2 len (all callers)
+    // one reflection of cv::borderInterpolate(BORDER_REFLECT_101): all of it for -len < p < 2 len - 1 (the pyramid and
+    // Scharr kernels' callers); refl_c below repeats it for the tracker's windows
     if (len == 1) return 0;
     if (p < 0) p = -p;
     if (p >= len) p = 2 * len - p - 2;
@@ -324,9 +326,22 @@ __device__ __forceinline__ float row_sum(float q) {
     return q;
 }
 
-// REFLECT_101 then clamped: task pixels past the window (never summed) may lie beyond one reflection on a small
-// top level; their addresses stay in the image
-__device__ __forceinline__ int refl_c(int p, int len) { return min(max(refl(p, len), 0), len - 1); }
+// cv::borderInterpolate(BORDER_REFLECT_101) for any p: reflected until it lies in the image (period 2 len - 2).  One
+// reflection is all a level larger than the window needs (every upper level, and every p then lies within win + 1 of
+// the image); a level-0 image with a side <= win is accepted too, and there summed window pixels and their bilinear
+// partners lie several reflections out.  The loop is not entered otherwise.
+__device__ __forceinline__ int refl_c(int p, int len) {
+    int q = refl(p, len);
+    while (q < 0 || q >= len) q = refl(q, len);
+    return q;
+}
+
+// floor(v) as an int for every float: INT_MIN where it does not fit (NaN, an infinity, |v| >= 2^31), as cvFloor gives
+// on x86 and the oracle's lk_floor; the range check after each use then rejects the point before anything is read
+__device__ __forceinline__ int floor_int(float v) {
+    const float f = floorf(v);
+    return fabsf(f) < 2147483648.f ? (int)f : INT_MIN;
+}
 
 // the (S + 1) x (S + 1) bilinear footprint of a lane's task, top-left (x0, y0), REFLECT_101 outside the image.
 // Inside the image each row's S + 1 <= 4 bytes come from one dword-aligned dwordx2 and one v_alignbyte (the aligned
@@ -510,7 +525,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S <= 2 ? 8 
         nyo = ny;
         px -= halfw;
         py -= halfw;
-        const int ipx = (int)floorf(px), ipy = (int)floorf(py);
+        const int ipx = floor_int(px), ipy = floor_int(py);
         if (ipx < -win || ipx >= Wl || ipy < -win || ipy >= Hl) {
             if (level == 0) {
                 status = 0;
@@ -565,7 +580,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S <= 2 ? 8 
         ny -= halfw;
         float pdx = 0.f, pdy = 0.f;
         for (int it = 0; it < P.max_count; ++it) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+            const int inx = floor_int(nx), iny = floor_int(ny);
             if (inx < -win || inx >= Wl || iny < -win || iny >= Hl) {
                 if (level == 0) status = 0;
                 break;
@@ -609,7 +624,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(S <= 2 ? 8 
         }
         if (status && level == 0) {
             const float ex = nxo - halfw, ey = nyo - halfw;
-            const int inx = (int)floorf(ex), iny = (int)floorf(ey);
+            const int inx = floor_int(ex), iny = floor_int(ey);
             if (inx < -win || inx >= Wl || iny < -win || iny >= Hl) {
                 status = 0;
             } else {
