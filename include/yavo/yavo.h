@@ -187,6 +187,32 @@ int yv_set_brief_steering(yv_ctx* ctx, int n_bins, int radius, const int16_t* di
 int yv_orient(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, const int32_t* rc, int n,
               int32_t* moments /* [n][2] = (m10, m01) */, uint8_t* bin /* [n] */);
 
+/* ---- sub-pixel stereo disparity: a SAD search and a parabola (beyond the reference; exact, all integer) ---- */
+/* With L and R the raw (unblurred) images of a rectified pair, a match of the left keypoint (r, c) and the right
+ * keypoint (r2, c2) (x = row, y = column; the rows may differ), a half window w in 1..7 and a search range s in 1..8:
+ *   inside iff r - w >= 0, r + w < H, c - w >= 0, c + w < W, r2 - w >= 0, r2 + w < H, c2 - s - w >= 0 and
+ *     c2 + s + w < W; otherwise status YV_SUBPIX_OUTSIDE, dcol_q8 = 0, sad = -1 and nothing is read (no clamp, no wrap);
+ *   SAD_k = sum over dr, dc in [-w, w] of |L(r + dr, c + dc) - R(r2 + dr, c2 + k + dc)| for k in -s..s, and k* the
+ *     first minimum in the order 0, -1, +1, -2, +2, ..., -s, +s;
+ *   |k*| = s: status YV_SUBPIX_EDGE, dcol_q8 = 0, sad = SAD_k* (the minimum is not bracketed);
+ *   otherwise a = SAD_(k*-1), b = SAD_k*, c = SAD_(k*+1), den = a + c - 2 b (>= |a - c|), frac = 0 for den = 0, else
+ *     floor((256 (a - c) + den) / (2 den)) (the parabola's vertex in 1/256 pixel, rounded half up, |frac| <= 128):
+ *     status YV_SUBPIX_OK, dcol_q8 = 256 k* + frac, sad = b.
+ * The refined right column is (double)c2 + (double)dcol_q8 * (1.0 / 256.0), exact in double. */
+#define YV_SUBPIX_NONE 0     /* not attempted (batches only): dcol_q8 = 0, sad = -1 */
+#define YV_SUBPIX_OK 1
+#define YV_SUBPIX_OUTSIDE 2
+#define YV_SUBPIX_EDGE 3
+#define YV_SUBPIX_DROP_EDGE 1 /* yv_batch_set_stereo_subpix flag: the tracks drop the YV_SUBPIX_EDGE matches */
+/* The refinement of n match records (pt1 = the left keypoint, pt2 = the right one; every record is attempted) on two
+ * H x W host images with rows `stride` bytes apart; dcol_q8, sad and status have capacity n.  Checked before the
+ * context: YV_ERR_INVALID for a NULL left, right, m, dcol_q8, sad or status with n > 0, n < 0, H < 9, W < 9,
+ * stride < W, half_win outside 1..7, search outside 1..8 or a keypoint outside the image; YV_ERR_CAPACITY for n > 4096;
+ * then, as in yv_match_knn2, YV_ERR_NODEVICE for a NULL context on a machine without a GPU. */
+int yv_stereo_subpix(yv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W, int stride,
+                     const yv_match* m, int n, int half_win, int search, int32_t* dcol_q8, int32_t* sad,
+                     uint8_t* status);
+
 /* ---- batched device pipeline (inputs resident in HBM) ---------------------------------------------- */
 /* A batch owns device workspace for up to max_images images of H x W and max_pairs match pairs.  Slot
  * index max_images is the "carry" slot: it holds the keypoints / descriptors of one image of the
@@ -236,6 +262,32 @@ int yv_batch_orient_view_get(yv_batch* b, yv_batch_orient_view* v);
  * buffers are allocated by the first call that sets gates.  YV_ERR_INVALID for a NULL batch, n_pairs different from
  * the batch's pair count, or a gate yv_match_gated would reject. */
 int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates /* [4 * n_pairs] */, int n_pairs);
+/* The stereo pairs (indices into yv_batch_set_pairs' list; query = left image, train = right image) whose matches the
+ * following runs refine as yv_stereo_subpix does, on the raw images passed to the run; pair_idx == NULL or n == 0
+ * switches it off (the default; the other arguments are then ignored).  With it on, yv_batch_run launches the
+ * refinement right after the match stage's finalize (inside stage 4 of yv_batch_stage_times) for every match of a
+ * marked pair that removeOutliers keeps (distance < limit, train index >= 0), that the match filter, when on, keeps,
+ * and whose two slots are images of the run (index < n_images); every other entry of the arrays below is
+ * YV_SUBPIX_NONE.  yv_batch_track, yv_batch_track_map and the LK mode then triangulate a match with status
+ * YV_SUBPIX_OK from its refined right column and every other match from its integer column, exactly as before; with
+ * flags = YV_SUBPIX_DROP_EDGE a YV_SUBPIX_EDGE match counts as not kept there.  Without it the edge set (edge_count,
+ * edge_query, edge_uv) is the unrefined run's and only edge_X moves, as long as every refined point still passes
+ * triangulate2View's test (s4 / s3 < 1e-2 and Z > 0), which is applied to the refined point: a match whose refined
+ * point fails it is no edge, one whose integer point failed it and whose refined point passes is.  A call waits for the
+ * device (a run or a track in flight on any stream reads the list and the arrays).  yv_batch_set_pairs switches it
+ * off.  The device
+ * arrays are allocated by the first call that switches it on; every call that switches it on fills them with
+ * YV_SUBPIX_NONE.  YV_ERR_INVALID for a NULL batch, n < 0, an index outside the pair list, a duplicate, a pair that
+ * names the carry slot, half_win outside 1..7, search outside 1..8 or flags outside 0..1. */
+int yv_batch_set_stereo_subpix(yv_batch* b, const int32_t* pair_idx /* [n] */, int n, int half_win, int search,
+                               int flags);
+typedef struct yv_batch_subpix_view {
+    const int32_t* dcol_q8;           /* [max_pairs][max_kp], by query keypoint index */
+    const int32_t* sad;               /* [max_pairs][max_kp] */
+    const uint8_t* status;            /* [max_pairs][max_kp] YV_SUBPIX_* */
+} yv_batch_subpix_view;
+/* Device views of the refinement's arrays (the last run with it on); YV_ERR_INVALID before it was ever switched on. */
+int yv_batch_subpix_view_get(yv_batch* b, yv_batch_subpix_view* v);
 /* Tracking (PnP) over the last run's matches: track t = {stereo_pair, temporal_pair} (pair indices of
  * yv_batch_set_pairs) where the stereo pair's query image (frame k left) is the temporal pair's train
  * image.  Each frame-(k-1) keypoint kept by removeOutliers in the temporal pair whose frame-k keypoint is

@@ -34,6 +34,12 @@ int yv_f_ransac(struct yv_ctx* ctx, const yv_match* m, int n, const int32_t* sam
 int yv_triangulate(struct yv_ctx* ctx, const double pose_a[7], const double pose_b[7], const double K[9],
                    const yv_match* m, int n, double* Xw, uint8_t* ok, int* n_ok);
 
+/* yv_triangulate from refined right columns (yv_stereo_subpix, yavo.h): record i's pt2 enters pixel2camera with the
+ * column (double)pt2.y + (double)dcol_q8[i] * (1.0 / 256.0) in place of (double)pt2.y, everything else operation for
+ * operation as in yv_triangulate.  dcol_q8 == NULL is exactly yv_triangulate. */
+int yv_triangulate_subpix(struct yv_ctx* ctx, const double pose_a[7], const double pose_b[7], const double K[9],
+                          const yv_match* m, const int32_t* dcol_q8, int n, double* Xw, uint8_t* ok, int* n_ok);
+
 /* Frame::world2Camera (src/Frame.cc:16-28): out[i] = K [R|t] [X_i; 1] (unnormalised). */
 int yv_world2camera(struct yv_ctx* ctx, const double* X, int n, const double pose[7], const double K[9],
                     double* out);

@@ -35,6 +35,9 @@ assert KEYPOINT_DTYPE.itemsize == 48 and MATCH_DTYPE.itemsize == 100
 MATCH2_DTYPE = np.dtype([("d1", "<i4"), ("j1", "<i4"), ("d2", "<i4"), ("j2", "<i4")])
 YV_MATCH_RATIO = 1
 YV_MATCH_MUTUAL = 2
+# yv_stereo_subpix: the status of a refined match, and yv_batch_set_stereo_subpix's flag
+YV_SUBPIX_NONE, YV_SUBPIX_OK, YV_SUBPIX_OUTSIDE, YV_SUBPIX_EDGE = 0, 1, 2, 3
+YV_SUBPIX_DROP_EDGE = 1
 
 # cv::GaussianBlur(Size(9, 9), 2.5) 8U fixed-point kernel (src/BriefDescriptor.cc:90)
 DEFAULT_BLUR_KERNEL = np.array([12, 22, 31, 41, 44, 41, 31, 22, 12], dtype=np.uint16)
@@ -65,6 +68,10 @@ class _BatchMatch2View(ctypes.Structure):
 
 class _BatchOrientView(ctypes.Structure):
     _fields_ = [("bin", ctypes.c_void_p), ("moments", ctypes.c_void_p)]
+
+
+class _BatchSubpixView(ctypes.Structure):
+    _fields_ = [("dcol_q8", ctypes.c_void_p), ("sad", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
 _lib: Optional[ctypes.CDLL] = None
@@ -106,6 +113,9 @@ SIGNATURES = {
     "yv_set_brief_steering": (_I, [_P, _I, _I, _P, _P]),
     "yv_orient": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P]),
     "yv_batch_orient_view_get": (_I, [_P, ctypes.POINTER(_BatchOrientView)]),
+    "yv_stereo_subpix": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "yv_batch_set_stereo_subpix": (_I, [_P, _P, _I, _I, _I, _I]),
+    "yv_batch_subpix_view_get": (_I, [_P, ctypes.POINTER(_BatchSubpixView)]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -125,6 +135,7 @@ _D = ctypes.c_double
 GEOM_SIGNATURES = {
     "yv_f_ransac": (_I, [_P, _P, _I, _P, _I, _D, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "yv_triangulate": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, ctypes.POINTER(_I)]),
+    "yv_triangulate_subpix": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _P, ctypes.POINTER(_I)]),
     "yv_world2camera": (_I, [_P, _P, _I, _P, _P, _P]),
     "yv_pose_lm": (_I, [_P, _P, _P, _I, _P, _P, _P, ctypes.POINTER(_I)]),
     "yv_pose_gn": (_I, [_P, _P, _P, _I, _P, _P, ctypes.POINTER(_I)]),
@@ -319,15 +330,25 @@ class _GeomMixin:
                                     ctypes.byref(mi), ctypes.byref(found)), "yv_f_ransac")
         return bool(found.value), F.reshape(3, 3), mi.value
 
-    def triangulate(self, pose_a, pose_b, K, matches: np.ndarray):
-        """triangulate2View per-match part -> (n_ok, Xw [n,3], ok [n] bool)."""
+    def triangulate(self, pose_a, pose_b, K, matches: np.ndarray, dcol_q8=None):
+        """triangulate2View per-match part -> (n_ok, Xw [n,3], ok [n] bool).  dcol_q8 [n] (stereo_subpix's): record
+        i's right column is pt2.y + dcol_q8[i] / 256 (yv_triangulate_subpix); None: the integer column."""
         m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
         pa, pb, k = _f64(pose_a, 7), _f64(pose_b, 7), _f64(K, 9)
         X = np.zeros((max(len(m), 1), 3))
         ok = np.zeros(max(len(m), 1), np.uint8)
         n = ctypes.c_int()
-        _check(self.lib.yv_triangulate(self.handle, _ptr(pa), _ptr(pb), _ptr(k), _ptr(m), len(m), _ptr(X), _ptr(ok),
-                                       ctypes.byref(n)), "yv_triangulate")
+        if dcol_q8 is None:
+            _check(self.lib.yv_triangulate(self.handle, _ptr(pa), _ptr(pb), _ptr(k), _ptr(m), len(m), _ptr(X),
+                                           _ptr(ok), ctypes.byref(n)), "yv_triangulate")
+        else:
+            dq = np.ascontiguousarray(dcol_q8, dtype=np.int32).reshape(-1)
+            if len(dq) != len(m):
+                raise ValueError("matches and dcol_q8 differ in length")
+            if len(dq) == 0:  # an empty array has no address to pass
+                dq = np.zeros(1, np.int32)
+            _check(self.lib.yv_triangulate_subpix(self.handle, _ptr(pa), _ptr(pb), _ptr(k), _ptr(m), _ptr(dq), len(m),
+                                                  _ptr(X), _ptr(ok), ctypes.byref(n)), "yv_triangulate_subpix")
         return n.value, X[:len(m)], ok[:len(m)].astype(bool)
 
     def world2camera(self, X, pose, K):
@@ -586,6 +607,31 @@ class Context(_GeomMixin):
                "yv_match_gated")
         return nn2[:nq].copy(), rev[:nt].copy()
 
+    def stereo_subpix(self, left: np.ndarray, right: np.ndarray, matches: np.ndarray, half_win: int = 5,
+                      search: int = 3) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """yv_stereo_subpix: the SAD search of +-search columns over (2 half_win + 1)^2 windows and the parabola
+        through its minimum, for every record (pt1 in left, pt2 in right; the raw images, equal shapes and strides)
+        -> (dcol_q8 [n] int32, sad [n] int32, status [n] uint8 YV_SUBPIX_*)."""
+        if left.dtype != np.uint8 or left.ndim != 2 or left.strides[1] != 1:
+            left = np.ascontiguousarray(left, dtype=np.uint8)
+        if right.dtype != np.uint8 or right.ndim != 2 or right.strides != left.strides:
+            right = np.ascontiguousarray(right, dtype=np.uint8)
+            left = np.ascontiguousarray(left)
+        if left.shape != right.shape:
+            raise ValueError("left and right differ in shape")
+        H, W = left.shape
+        m = np.ascontiguousarray(matches, dtype=MATCH_DTYPE)
+        n = len(m)
+        if n == 0:  # an empty array has no address to pass
+            m = np.zeros(1, MATCH_DTYPE)
+        dq = np.zeros(max(n, 1), np.int32)
+        sad = np.zeros(max(n, 1), np.int32)
+        st = np.zeros(max(n, 1), np.uint8)
+        _check(self.lib.yv_stereo_subpix(self.handle, _ptr(left), _ptr(right), H, W, int(left.strides[0]), _ptr(m), n,
+                                         int(half_win), int(search), _ptr(dq), _ptr(sad), _ptr(st)),
+               "yv_stereo_subpix")
+        return dq[:n].copy(), sad[:n].copy(), st[:n].copy()
+
     def match_robust(self, q: np.ndarray, t: np.ndarray, thr: int = 20, ratio=(4, 5),
                      mutual: bool = True) -> Tuple[np.ndarray, np.ndarray]:
         """yv_match_robust: matchFeatures + removeOutliers(thr) + Lowe's ratio test d1 * den < d2 * num (ratio =
@@ -724,6 +770,26 @@ class Batch:
         _check(self.lib.yv_batch_match2_view_get(self.handle, ctypes.byref(v)), "yv_batch_match2_view_get")
         return v
 
+
+    def set_stereo_subpix(self, pairs=None, half_win: int = 5, search: int = 3, drop_edge: bool = False) -> None:
+        """The sub-pixel refinement of the following runs (yv_batch_set_stereo_subpix): pairs = indices into set_pairs'
+        list of the stereo pairs (left = query) to refine with a (2 half_win + 1)^2 window over +-search columns; None
+        or empty (the default) switches it off.  drop_edge: the tracks drop the matches whose SAD minimum lies on the
+        edge of the search range."""
+        if pairs is None or len(pairs) == 0:
+            _check(self.lib.yv_batch_set_stereo_subpix(self.handle, None, 0, 0, 0, 0), "yv_batch_set_stereo_subpix")
+            return
+        p = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1))
+        _check(self.lib.yv_batch_set_stereo_subpix(self.handle, _ptr(p), len(p), int(half_win), int(search),
+                                                   YV_SUBPIX_DROP_EDGE if drop_edge else 0),
+               "yv_batch_set_stereo_subpix")
+
+    def subpix_view(self) -> _BatchSubpixView:
+        """Device arrays of the sub-pixel refinement (yv_batch_subpix_view_get; after set_stereo_subpix switched it
+        on): dcol_q8 and sad [max_pairs][max_kp] int32, status [max_pairs][max_kp] uint8, by query keypoint."""
+        v = _BatchSubpixView()
+        _check(self.lib.yv_batch_subpix_view_get(self.handle, ctypes.byref(v)), "yv_batch_subpix_view_get")
+        return v
 
     def orient_view(self) -> _BatchOrientView:
         """Device arrays of the keypoints' orientation (yv_batch_orient_view_get; after a run with steering on): bin

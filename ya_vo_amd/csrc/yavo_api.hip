@@ -750,6 +750,49 @@ int yv_match_robust(yv_ctx* ctx, const yv_keypoint* q, int nq, const yv_keypoint
     return YV_OK;
 }
 
+int yv_stereo_subpix(yv_ctx* ctx, const uint8_t* left, const uint8_t* right, int H, int W, int stride,
+                     const yv_match* m, int n, int half_win, int search, int32_t* dcol_q8, int32_t* sad,
+                     uint8_t* status) {
+    if (n < 0 || H < 9 || W < 9 || stride < W || half_win < 1 || half_win > yavo::kSubpixMaxWin || search < 1 ||
+        search > yavo::kSubpixMaxSearch || (n > 0 && (!left || !right || !m || !dcol_q8 || !sad || !status)))
+        return YV_ERR_INVALID;
+    if (n > yavo::kMaxKp) return YV_ERR_CAPACITY;
+    for (int i = 0; i < n; ++i) {
+        const yv_keypoint &a = m[i].pt1, &b = m[i].pt2;
+        if (a.x < 0 || a.x >= H || a.y < 0 || a.y >= W || b.x < 0 || b.x >= H || b.y < 0 || b.y >= W)
+            return YV_ERR_INVALID;
+    }
+    if (!ctx) return yv_device_count() > 0 ? YV_ERR_INVALID : YV_ERR_NODEVICE;
+    if (n == 0) return YV_OK;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = ctx->stream;
+    // the images keep the caller's stride and end with their last pixel, (H - 1) * stride + W bytes: the kernel's bound
+    const size_t span = (size_t)(H - 1) * (size_t)stride + (size_t)W;
+    Arena a{ctx};
+    uint8_t *dl, *dr, *dst;
+    yv_match* dm;
+    int32_t *ddq, *dsad;
+    a.add(&dl, span);
+    a.add(&dr, span);
+    a.add(&dm, (size_t)n);
+    a.add_host(&ddq, (size_t)n);
+    a.add_host(&dsad, (size_t)n);
+    a.add_host(&dst, (size_t)n);
+    if (a.commit() != YV_OK) return YV_ERR_HIP;
+    a.in(dl, left, span);
+    a.in(dr, right, span);
+    a.in(dm, m, sizeof(yv_match) * (size_t)n);
+    YV_HIP(a.upload(s));
+    yavo::launch_subpix_list(dl, dr, H, W, stride, dm, n, half_win, search, yavo::SubpixOut{ddq, dsad, dst}, s);
+    if (check_launch() != YV_OK) return YV_ERR_HIP;
+    a.out(dcol_q8, ddq, sizeof(int32_t) * (size_t)n);
+    a.out(sad, dsad, sizeof(int32_t) * (size_t)n);
+    a.out(status, dst, (size_t)n);
+    YV_HIP(a.fetch(s));
+    return YV_OK;
+}
+
 // Test entry point (tests/test_gpu_brief_persistent.py; like yv_debug_xlane not part of the public headers): caps the
 // number of brief_kernel's workers for the context's later launches, so that few workers walk many bands; 0 restores
 // the default (two per CU).

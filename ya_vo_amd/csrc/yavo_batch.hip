@@ -49,6 +49,43 @@ yavo::MatchRecords match_records(const yv_batch* b) {
     return {b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj, b->match_lim};
 }
 
+static_assert(YV_SUBPIX_NONE == yavo::kSubpixNone && YV_SUBPIX_OK == yavo::kSubpixOk &&
+                  YV_SUBPIX_OUTSIDE == yavo::kSubpixOutside && YV_SUBPIX_EDGE == yavo::kSubpixEdge,
+              "yavo.h / yavo_internal.h");
+
+// the stereo refinement's arrays everywhere "not attempted" (dcol_q8 0, sad -1, status NONE), on s
+int subpix_fill_none(yv_batch* b, hipStream_t s) {
+    const size_t n = (size_t)std::max(b->max_pairs, 1) * (size_t)b->max_kp;
+    YV_HIP(hipMemsetAsync(b->subpix_dcol, 0, n * sizeof(int32_t), s));
+    YV_HIP(hipMemsetAsync(b->subpix_sad, 0xFF, n * sizeof(int32_t), s));
+    YV_HIP(hipMemsetAsync(b->subpix_status, YV_SUBPIX_NONE, n, s));
+    return YV_OK;
+}
+
+// the stereo refinement's device buffers, on first use
+int ensure_subpix(yv_batch* b) {
+    if (b->subpix_alloc) return YV_OK;
+    const size_t nk = (size_t)b->max_kp, np = (size_t)std::max(b->max_pairs, 1);
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->subpix_pairs, np);
+    rc |= b->mem.alloc(&b->subpix_dcol, np * nk);
+    rc |= b->mem.alloc(&b->subpix_sad, np * nk);
+    rc |= b->mem.alloc(&b->subpix_status, np * nk);
+    if (rc != YV_OK) {  // a retry starts clean
+        b->mem.release(b->subpix_pairs, b->subpix_dcol, b->subpix_sad, b->subpix_status);
+        return YV_ERR_HIP;
+    }
+    b->subpix_alloc = true;
+    return YV_OK;
+}
+
+// what the track builders read of the refinement (nullptr while it is off: the unrefined kernels)
+const yavo::SubpixUse* subpix_use(const yv_batch* b, yavo::SubpixUse* u) {
+    if (!b->subpix_on) return nullptr;
+    *u = {b->subpix_dcol, b->subpix_status, (b->subpix_flags & YV_SUBPIX_DROP_EDGE) != 0};
+    return u;
+}
+
 }  // namespace
 
 namespace yavo {
@@ -344,7 +381,51 @@ int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs, int n_pairs) {
     b->n_pairs = n_pairs;
     b->n_tracks = 0;  // tracks refer to pair indices: set them again
     b->gated = false;  // and so do the gates
+    b->subpix_on = false;  // and the pairs marked for the stereo refinement
     return upload_pairs_rev(b);
+}
+
+int yv_batch_set_stereo_subpix(yv_batch* b, const int32_t* pair_idx, int n, int half_win, int search, int flags) {
+    if (!b || n < 0) return YV_ERR_INVALID;
+    if (!pair_idx || n == 0) {
+        b->subpix_on = false;
+        return YV_OK;
+    }
+    if (half_win < 1 || half_win > yavo::kSubpixMaxWin || search < 1 || search > yavo::kSubpixMaxSearch || flags < 0 ||
+        flags > YV_SUBPIX_DROP_EDGE || n > b->n_pairs)
+        return YV_ERR_INVALID;
+    std::vector<uint8_t> seen((size_t)b->n_pairs, 0);
+    for (int i = 0; i < n; ++i) {
+        const int p = pair_idx[i];
+        if (p < 0 || p >= b->n_pairs || seen[p]) return YV_ERR_INVALID;
+        if (b->h_pairs[2 * p] >= b->max_images || b->h_pairs[2 * p + 1] >= b->max_images) return YV_ERR_INVALID;
+        seen[p] = 1;
+    }
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    const int rc = ensure_subpix(b);
+    if (rc != YV_OK) return rc;
+    // a run or an edge build in flight, on the context's stream, the batch's or one of the caller's, reads the list
+    // and the arrays: wait for the device
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipDeviceSynchronize());
+    b->build_pending = false;
+    YV_HIP(hipMemcpyAsync(b->subpix_pairs, pair_idx, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, s));
+    if (subpix_fill_none(b, s) != YV_OK) return YV_ERR_HIP;
+    YV_HIP(hipStreamSynchronize(s));
+    b->subpix_n = n;
+    b->subpix_win = half_win;
+    b->subpix_search = search;
+    b->subpix_flags = flags;
+    b->subpix_on = true;
+    return YV_OK;
+}
+
+int yv_batch_subpix_view_get(yv_batch* b, yv_batch_subpix_view* v) {
+    if (!b || !v || !b->subpix_alloc) return YV_ERR_INVALID;
+    v->dcol_q8 = b->subpix_dcol;
+    v->sad = b->subpix_sad;
+    v->status = b->subpix_status;
+    return YV_OK;
 }
 
 int yv_batch_set_match_gates(yv_batch* b, const int32_t* gates, int n_pairs) {
@@ -512,6 +593,12 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
         st.kp_count_copy = copy_counts ? b->kp_count_build : nullptr;
         st.n_slots = b->nslots;
         rc |= match_stage(b, st, s, run);
+        // the stereo refinement of the marked pairs, on the finalize's match_dj / match_lim / keep and the raw images
+        if (b->subpix_on)
+            yavo::launch_subpix_batch(d_images, n_images, H, W, stride, image_pitch, b->subpix_pairs, b->subpix_n,
+                                      b->pairs, b->keypoints, b->kp_count, b->match_dj, b->match_lim,
+                                      b->run_flags ? b->keep : nullptr, K, b->subpix_win, b->subpix_search,
+                                      yavo::SubpixOut{b->subpix_dcol, b->subpix_sad, b->subpix_status}, s);
     } else {
         rc |= record_stage(b, s, run, 4);
     }
@@ -757,6 +844,7 @@ int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stre
     const bool timed = b->timing == 1 && run >= 0 && !b->tracked[run];
     hipEvent_t* ev = timed ? &b->events[(size_t)run * kEvPerRun] : nullptr;
     const hipStream_t s_run = s;
+    yavo::SubpixUse sub_use{};
     double* lkX = nullptr;
     float* lkP = nullptr;
     int32_t *lkQ = nullptr, *lkC = nullptr;
@@ -775,7 +863,7 @@ int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stre
         b->lk_ev_pending[lk_j] = false;
         yavo::launch_stereo_points(b->lk_sp, b->n_tracks, b->pairs, b->keypoints, b->kp_count, b->match_dj,
                                    b->match_lim, b->max_kp, b->track_K, b->T_right, lkX, lkP, lkQ, lkC, s_run,
-                                   b->run_flags ? b->keep : nullptr);
+                                   b->run_flags ? b->keep : nullptr, subpix_use(b, &sub_use));
     }
     const int32_t* build_counts = b->kp_count;
     if (b->overlap && b->build_async) {
@@ -811,7 +899,7 @@ int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stre
     } else {
         yavo::launch_track_build(b->tracks, b->n_tracks, b->pairs, b->keypoints, build_counts, b->match_dj,
                                  b->match_lim, b->max_kp, b->track_K, b->T_right, eX, euv, eq, ec, s,
-                                 b->run_flags ? b->keep : nullptr);
+                                 b->run_flags ? b->keep : nullptr, subpix_use(b, &sub_use));
     }
     if (b->overlap) YV_HIP(hipEventRecord(b->ev_edges[k], s));
     if (s != s_run && b->lk_step == 0) {  // (the LK stage reads nothing the next run writes: no join)

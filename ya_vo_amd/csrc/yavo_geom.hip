@@ -545,11 +545,16 @@ __device__ bool eigen_jacobi_svd4(const double (&Ain)[16], double (&sv)[4], doub
 
 // LoopHandler::triangulation of one match (pixel2camera of both integer pixels, DLT rows, Eigen JacobiSVD);
 // returns success (s4/s3 < 1e-2) && Z > 0, the triangulate2View acceptance test (src/LoopHandler.cc:676)
+// SUBPIX (yv_stereo_subpix's refinement): the second pixel's column is y2 + dq / 256 (exact in double: |dq| < 2^12 and
+// y2 < 2^31 leave the sum inside 53 bits) in place of y2; nothing else changes.
+template <bool SUBPIX = false>
 __device__ bool triangulate_px(int x1, int y1, int x2, int y2, const double* Ta, const double* Tb,
-                               const double* K, double* Xo) {
+                               const double* K, double* Xo, int dq = 0) {
     const double K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
+    double y2d = (double)y2;
+    if constexpr (SUBPIX) y2d = (double)y2 + (double)dq * (1.0 / 256.0);
     const double pa[2] = {((double)x1 - K2) * 1.0 / K0, ((double)y1 - K5) * 1.0 / K4};
-    const double pb[2] = {((double)x2 - K2) * 1.0 / K0, ((double)y2 - K5) * 1.0 / K4};
+    const double pb[2] = {((double)x2 - K2) * 1.0 / K0, (y2d - K5) * 1.0 / K4};
     double A[16];
 #pragma unroll
     for (int v = 0; v < 2; ++v) {
@@ -583,13 +588,17 @@ __device__ bool triangulate_px(int x1, int y1, int x2, int y2, const double* Ta,
     return s && X2 > 0;
 }
 
+template <bool SUBPIX>
 __global__ __launch_bounds__(256) void triangulate_kernel(const yv_match* __restrict__ m, int n, const double* __restrict__ poses /*[2][7]*/,
                                    const double* __restrict__ K, double* __restrict__ Xw, uint8_t* __restrict__ ok,
-                                   int32_t* __restrict__ n_ok) {
+                                   int32_t* __restrict__ n_ok, const int32_t* __restrict__ dcol_q8) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     bool good = false;
     if (i < n) {
-        good = triangulate_px(m[i].pt1.x, m[i].pt1.y, m[i].pt2.x, m[i].pt2.y, poses, poses + 7, K, Xw + 3 * i);
+        int dq = 0;
+        if constexpr (SUBPIX) dq = dcol_q8[i];
+        good = triangulate_px<SUBPIX>(m[i].pt1.x, m[i].pt1.y, m[i].pt2.x, m[i].pt2.y, poses, poses + 7, K, Xw + 3 * i,
+                                      dq);
         ok[i] = good ? 1 : 0;
     }
     if (!n_ok) return;  // the host counts ok[] (yv_triangulate)
@@ -1436,13 +1445,16 @@ __global__ __launch_bounds__(NT) YAVO_LM_ATTR void pose_lm_kernel(const int32_t*
 // src/LoopHandler.cc:658-726).  uv = (kp_{k-1}[i].x, kp_{k-1}[i].y) (the reference's measurement,
 // src/LoopHandler.cc:786).  Edges keep temporal query order.  One workgroup per track.
 // KEEP (the match filter is on): a temporal match i counts only if keep[tp][i], its stereo match only if keep[sp][j].
-template <int NT, bool KEEP>
+// SUBPIX (the stereo refinement is on): the stereo match triangulates from its refined right column (sub_dcol[sp][j],
+// zero unless its status is OK) and, with drop_edge, does not count when its status is EDGE.
+template <int NT, bool KEEP, bool SUBPIX>
 __global__ __launch_bounds__(NT) void track_build_kernel(
     const int32_t* __restrict__ tracks, const int32_t* __restrict__ pairs, const yv_keypoint* __restrict__ keypoints,
     const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj, const int32_t* __restrict__ match_lim,
     int max_kp, const double* __restrict__ Kall, const double* __restrict__ T_right, double* __restrict__ edge_X,
     double* __restrict__ edge_uv, int32_t* __restrict__ edge_query, int32_t* __restrict__ edge_count,
-    const uint8_t* __restrict__ keep) {
+    const uint8_t* __restrict__ keep, const int32_t* __restrict__ sub_dcol, const uint8_t* __restrict__ sub_status,
+    int drop_edge) {
     __shared__ int s_tmp[40];
     __shared__ double s_K[9], s_Ta[7], s_Tb[7];
     const int t = blockIdx.x, tid = threadIdx.x;
@@ -1478,8 +1490,13 @@ __global__ __launch_bounds__(NT) void track_build_kernel(
                 const int2 b = dj_s[a.y];
                 bool ks = true;
                 if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + a.y] != 0;
+                int dq = 0;
+                if constexpr (SUBPIX) {
+                    dq = sub_dcol[(int64_t)sp * max_kp + a.y];
+                    if (drop_edge && sub_status[(int64_t)sp * max_kp + a.y] == kSubpixEdge) ks = false;
+                }
                 if (b.x < lim_s && b.y >= 0 && ks)
-                    good = triangulate_px(kl[a.y].x, kl[a.y].y, kr[b.y].x, kr[b.y].y, s_Ta, s_Tb, s_K, X);
+                    good = triangulate_px<SUBPIX>(kl[a.y].x, kl[a.y].y, kr[b.y].x, kr[b.y].y, s_Ta, s_Tb, s_K, X, dq);
             }
         }
         int tot = 0;
@@ -1502,13 +1519,15 @@ __global__ __launch_bounds__(NT) void track_build_kernel(
 // left keypoints whose stereo match (pair sp) survives removeOutliers and triangulates (left camera = world).
 // Compacted in keypoint order: X, the LK start point (x = column, y = row as cv::Point2f, :344) and the
 // keypoint index.  One workgroup per track.
-template <int NT, bool KEEP>
+// KEEP / SUBPIX: as in track_build_kernel.
+template <int NT, bool KEEP, bool SUBPIX>
 __global__ __launch_bounds__(NT) void stereo_points_kernel(
     const int32_t* __restrict__ stereo_pairs, const int32_t* __restrict__ pairs,
     const yv_keypoint* __restrict__ keypoints, const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj,
     const int32_t* __restrict__ match_lim, int max_kp, const double* __restrict__ Kall,
     const double* __restrict__ T_right, double* __restrict__ pX, float* __restrict__ pts, int32_t* __restrict__ pq,
-    int32_t* __restrict__ pcount, const uint8_t* __restrict__ keep) {
+    int32_t* __restrict__ pcount, const uint8_t* __restrict__ keep, const int32_t* __restrict__ sub_dcol,
+    const uint8_t* __restrict__ sub_status, int drop_edge) {
     __shared__ int s_tmp[40];
     __shared__ double s_K[9], s_Ta[7], s_Tb[7];
     const int t = blockIdx.x, tid = threadIdx.x;
@@ -1537,7 +1556,13 @@ __global__ __launch_bounds__(NT) void stereo_points_kernel(
             const int2 a = dj[j];
             bool ks = true;
             if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + j] != 0;
-            if (a.x < lim && a.y >= 0 && ks) good = triangulate_px(kl[j].x, kl[j].y, kr[a.y].x, kr[a.y].y, s_Ta, s_Tb, s_K, X);
+            int dq = 0;
+            if constexpr (SUBPIX) {
+                dq = sub_dcol[(int64_t)sp * max_kp + j];
+                if (drop_edge && sub_status[(int64_t)sp * max_kp + j] == kSubpixEdge) ks = false;
+            }
+            if (a.x < lim && a.y >= 0 && ks)
+                good = triangulate_px<SUBPIX>(kl[j].x, kl[j].y, kr[a.y].x, kr[a.y].y, s_Ta, s_Tb, s_K, X, dq);
         }
         int tot = 0;
         const int off = block_excl_scan_geom<NT>(good ? 1 : 0, s_tmp, &tot);
@@ -1720,9 +1745,14 @@ void launch_f_ransac(const yv_match* matches, int64_t list_stride, const int32_t
 }
 
 void launch_triangulate(const yv_match* m, int n, const double* poses2, const double* K, double* Xw, uint8_t* ok,
-                        int32_t* n_ok, hipStream_t s) {
+                        int32_t* n_ok, hipStream_t s, const int32_t* dcol_q8) {
     if (n <= 0) return;
-    hipLaunchKernelGGL(geom::triangulate_kernel, dim3((n + 255) / 256), dim3(256), 0, s, m, n, poses2, K, Xw, ok, n_ok);
+    if (dcol_q8)
+        hipLaunchKernelGGL(geom::triangulate_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, s, m, n, poses2, K, Xw,
+                           ok, n_ok, dcol_q8);
+    else
+        hipLaunchKernelGGL(geom::triangulate_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, s, m, n, poses2, K, Xw,
+                           ok, n_ok, dcol_q8);
 }
 
 void launch_world2camera(const double* X, int n, const double* T, const double* K, double* out, hipStream_t s) {
@@ -1743,34 +1773,57 @@ void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, con
 void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
                         const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
                         const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s, const uint8_t* keep) {
+                        int32_t* edge_count, hipStream_t s, const uint8_t* keep, const SubpixUse* sub) {
     if (n_tracks <= 0) return;
+    const int32_t* sd = sub ? sub->dcol_q8 : nullptr;
+    const uint8_t* ss = sub ? sub->status : nullptr;
+    const int de = sub && sub->drop_edge ? 1 : 0;
     // 1024 threads: about one query keypoint per thread (the FP64 triangulations are latency-bound; 256 / 512 were
     // measured)
-    if (keep)
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, true>), dim3(n_tracks), dim3(1024), 0, s, tracks, pairs,
-                           keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv, edge_query,
-                           edge_count, keep);
+    if (sub && keep)
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, true, true>), dim3(n_tracks), dim3(1024), 0, s, tracks,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
+                           edge_query, edge_count, keep, sd, ss, de);
+    else if (sub)
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, false, true>), dim3(n_tracks), dim3(1024), 0, s, tracks,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
+                           edge_query, edge_count, keep, sd, ss, de);
+    else if (keep)
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, true, false>), dim3(n_tracks), dim3(1024), 0, s, tracks,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
+                           edge_query, edge_count, keep, sd, ss, de);
     else
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, false>), dim3(n_tracks), dim3(1024), 0, s, tracks, pairs,
-                           keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv, edge_query,
-                           edge_count, keep);
+        hipLaunchKernelGGL((geom::track_build_kernel<1024, false, false>), dim3(n_tracks), dim3(1024), 0, s, tracks,
+                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
+                           edge_query, edge_count, keep, sd, ss, de);
 }
 
 void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
                           const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
                           const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep) {
+                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep,
+                          const SubpixUse* sub) {
     if (n_tracks <= 0) return;
+    const int32_t* sd = sub ? sub->dcol_q8 : nullptr;
+    const uint8_t* ss = sub ? sub->status : nullptr;
+    const int de = sub && sub->drop_edge ? 1 : 0;
     // 1024 threads: about one keypoint per thread (FP64 triangulations, latency-bound)
-    if (keep)
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true>), dim3(n_tracks), dim3(1024), 0, s, stereo_pairs,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts, pq, pcount,
-                           keep);
+    if (sub && keep)
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true, true>), dim3(n_tracks), dim3(1024), 0, s,
+                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
+                           pq, pcount, keep, sd, ss, de);
+    else if (sub)
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false, true>), dim3(n_tracks), dim3(1024), 0, s,
+                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
+                           pq, pcount, keep, sd, ss, de);
+    else if (keep)
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true, false>), dim3(n_tracks), dim3(1024), 0, s,
+                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
+                           pq, pcount, keep, sd, ss, de);
     else
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false>), dim3(n_tracks), dim3(1024), 0, s, stereo_pairs,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts, pq, pcount,
-                           keep);
+        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false, false>), dim3(n_tracks), dim3(1024), 0, s,
+                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
+                           pq, pcount, keep, sd, ss, de);
 }
 
 void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,

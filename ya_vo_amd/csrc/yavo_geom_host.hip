@@ -47,6 +47,11 @@ int yv_f_ransac(yv_ctx* ctx, const yv_match* m, int n, const int32_t* samples, i
 
 int yv_triangulate(yv_ctx* ctx, const double pose_a[7], const double pose_b[7], const double K[9], const yv_match* m,
                    int n, double* Xw, uint8_t* ok, int* n_ok) {
+    return yv_triangulate_subpix(ctx, pose_a, pose_b, K, m, nullptr, n, Xw, ok, n_ok);
+}
+
+int yv_triangulate_subpix(yv_ctx* ctx, const double pose_a[7], const double pose_b[7], const double K[9],
+                          const yv_match* m, const int32_t* dcol_q8, int n, double* Xw, uint8_t* ok, int* n_ok) {
     if (!ctx || !pose_a || !pose_b || !K || !n_ok || n < 0 || (n > 0 && (!m || !Xw || !ok))) return YV_ERR_INVALID;
     *n_ok = 0;
     if (n == 0) return YV_OK;
@@ -57,8 +62,10 @@ int yv_triangulate(yv_ctx* ctx, const double pose_a[7], const double pose_b[7], 
     yv_match* dm;
     double *dposes, *dK, *dX;
     uint8_t* dok;
+    int32_t* ddq = nullptr;
     // every record, pose and output is read or written once: all in the pinned mirror, no DMA
     a.add_host(&dm, (size_t)n);
+    if (dcol_q8) a.add_host(&ddq, (size_t)n);
     a.add_host(&dposes, 14);
     a.add_host(&dK, 9);
     a.add_host(&dX, 3 * (size_t)n);
@@ -68,7 +75,8 @@ int yv_triangulate(yv_ctx* ctx, const double pose_a[7], const double pose_b[7], 
     a.in(dposes, pose_a, sizeof(double) * 7);
     a.in(dposes + 7, pose_b, sizeof(double) * 7);
     a.in(dK, K, sizeof(double) * 9);
-    yavo::launch_triangulate(dm, n, dposes, dK, dX, dok, nullptr, s);
+    if (dcol_q8) a.in(ddq, dcol_q8, sizeof(int32_t) * (size_t)n);
+    yavo::launch_triangulate(dm, n, dposes, dK, dX, dok, nullptr, s, ddq);
     if (check_launch() != YV_OK) return YV_ERR_HIP;
     a.out(Xw, dX, sizeof(double) * 3 * (size_t)n);
     a.out(ok, dok, (size_t)n);

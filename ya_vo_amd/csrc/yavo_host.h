@@ -249,6 +249,13 @@ struct yv_batch {
     bool steer_alloc = false;
     uint8_t* steer_bin = nullptr;   // [slot][max_kp]
     int32_t* steer_mom = nullptr;   // [slot][max_kp][2] (m10, m01)
+    // the sub-pixel stereo refinement (yv_batch_set_stereo_subpix): allocated by the first call that switches it on
+    bool subpix_on = false, subpix_alloc = false;
+    int subpix_n = 0, subpix_win = 0, subpix_search = 0, subpix_flags = 0;
+    int32_t* subpix_pairs = nullptr;  // [max_pairs] the marked pairs
+    int32_t* subpix_dcol = nullptr;   // [max_pairs][max_kp] dcol_q8, by query keypoint
+    int32_t* subpix_sad = nullptr;    // [max_pairs][max_kp]
+    uint8_t* subpix_status = nullptr; // [max_pairs][max_kp]
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)

@@ -190,6 +190,31 @@ void launch_brief_steer(const uint8_t* blur, int n_images, int H, int W, const S
 // bin and moments alone of rc[0 .. min(*count, max_kp)) = {row, col}, any position of one H x W image
 void launch_orient(const uint8_t* blur, int H, int W, const SteerTables& t, const int32_t* rc, const int32_t* count,
                    int max_kp, uint8_t* bin, int32_t* moments, hipStream_t s);
+// Sub-pixel stereo refinement (yv_stereo_subpix / yv_batch_set_stereo_subpix, yavo_stereo_subpix.hip; the values of
+// YV_SUBPIX_*).  Images are read inside [image, image + (H - 1) * stride + W) only.
+constexpr int kSubpixNone = 0, kSubpixOk = 1, kSubpixOutside = 2, kSubpixEdge = 3;
+constexpr int kSubpixMaxWin = 7, kSubpixMaxSearch = 8;
+struct SubpixOut {
+    int32_t* dcol_q8;
+    int32_t* sad;
+    uint8_t* status;
+};
+// every record of m[0, n): pt1 in `left`, pt2 in `right`
+void launch_subpix_list(const uint8_t* left, const uint8_t* right, int H, int W, int stride, const yv_match* m, int n,
+                        int half_win, int search, const SubpixOut& out, hipStream_t s);
+// the kept matches of the pairs marked[0, n_marked) (indices into pairs) of a run on n_images images (image i at
+// images + i * pitch): out[pair][query] for every query in [0, max_kp), kSubpixNone where nothing is attempted
+void launch_subpix_batch(const uint8_t* images, int n_images, int H, int W, int stride, int64_t pitch,
+                         const int32_t* marked, int n_marked, const int32_t* pairs, const yv_keypoint* keypoints,
+                         const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim,
+                         const uint8_t* keep, int max_kp, int half_win, int search, const SubpixOut& out,
+                         hipStream_t s);
+// what the track builders read of it: [pair][max_kp] arrays; drop_edge: a kSubpixEdge match counts as not kept
+struct SubpixUse {
+    const int32_t* dcol_q8;
+    const uint8_t* status;
+    bool drop_edge;
+};
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
@@ -200,8 +225,9 @@ size_t f_ransac_ws_bytes(int n_lists, int iters);
 void launch_f_ransac(const yv_match* matches, int64_t list_stride, const int32_t* counts, int n_lists,
                      const int32_t* samples, int64_t sample_stride, int iters, double thr, double* F_out,
                      int32_t* max_inliers, int32_t* found, void* ws, hipStream_t s);
+// dcol_q8 (optional, [n]): record i's right column is pt2.y + dcol_q8[i] / 256 (yv_triangulate_subpix)
 void launch_triangulate(const yv_match* m, int n, const double* poses2, const double* K, double* Xw, uint8_t* ok,
-                        int32_t* n_ok, hipStream_t s);
+                        int32_t* n_ok, hipStream_t s, const int32_t* dcol_q8 = nullptr);
 void launch_world2camera(const double* X, int n, const double* T, const double* K, double* out, hipStream_t s);
 void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, const double* uv, const double* K,
                     double* poses, uint8_t* outlier, int32_t* inliers, hipStream_t s);
@@ -233,12 +259,14 @@ void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const
 void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
                         const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
                         const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s, const uint8_t* keep = nullptr);
+                        int32_t* edge_count, hipStream_t s, const uint8_t* keep = nullptr,
+                        const struct SubpixUse* sub = nullptr);
 // keep (optional, [pair][max_kp], the match filter's): a match counts only if its query's byte is set
 void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
                           const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
                           const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep = nullptr);
+                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep = nullptr,
+                          const struct SubpixUse* sub = nullptr);
 void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,
                      const int32_t* pcount, int max_kp, double* edge_X, double* edge_uv, int32_t* edge_query,
                      int32_t* edge_count, hipStream_t s);
