@@ -6,7 +6,9 @@
  *   getCalibParams            src/Utils.cc:39-62       first two lines of <seq>/calib.txt -> Camera Left / Right
  *   parseCalibString          src/Utils.cc:4-28        ' '-separated std::stod, unparsable tokens skipped
  *   cv::imread(path, 0)       src/LoopHandler.cc:919   PNG -> 8-bit grey
- * and adds the KITTI odometry pose writer / reader the reference lacks (needed for trajectory RMSE).
+ * and adds the KITTI odometry pose writer / reader the reference lacks (needed for trajectory RMSE), and the
+ * rectifier the reference leaves open (include/Image.hpp:11-13 "Write rectifier if necessary", Image::unDistort
+ * declared at :25 and never defined): yv_rectify_*, undistortion + rectification of decoded frames on the GPU.
  */
 #ifndef YAVO_IO_H
 #define YAVO_IO_H
@@ -84,6 +86,47 @@ int yv_pngdec_status(yv_pngdec* d, int32_t* codes, int* n_bad);
 /* the integrity checks of the following decodes (default both on, as libpng / zlib do): crc = every IDAT chunk's
  * CRC-32 (libpng png_set_crc_action), adler = the zlib Adler-32 trailer (libpng PNG_IGNORE_ADLER32 turns it off) */
 int yv_pngdec_set_checks(yv_pngdec* d, int crc, int adler);
+
+/* Lens undistortion and rectification on the GPU (yavo_rectify.hip), the stage between the
+ * decode and yv_batch_run for cameras whose frames are not rectified: cv::initUndistortRectifyMap + cv::remap
+ * (INTER_LINEAR, BORDER_CONSTANT 0) for 8-bit grey images, batched and device-resident.  u = column, v = row; camera
+ * matrices are row-major with fx, cx on the first row.
+ * A rectifier holds n_maps maps (1..16; 2 = left, right) from a src_H x src_W source to a dst_H x dst_W destination,
+ * all four sizes in 1..8192.  A map is int32 [dst_H][dst_W][2] = (qu, qv), the source column and row in 1/32 pixel;
+ * YV_RECTIFY_OUTSIDE in either component marks a destination pixel without a source.  The remap of a pixel with
+ * ix = qu >> 5, ax = qu & 31, iy = qv >> 5, ay = qv & 31 and tap(r, c) = src[r][c] inside the source, else 0 (never
+ * read, no clamp, no wrap), is ((32 - ay) * t + ay * b + 512) >> 10 with t = (32 - ax) * tap(iy, ix) + ax *
+ * tap(iy, ix + 1) and b the same on row iy + 1; an OUTSIDE pixel is 0. */
+#define YV_RECTIFY_OUTSIDE INT32_MIN
+typedef struct yv_rectify yv_rectify;
+int yv_rectify_create(struct yv_ctx* ctx, int n_maps, int src_H, int src_W, int dst_H, int dst_W, yv_rectify** out);
+void yv_rectify_destroy(yv_rectify* r);
+/* the map of a camera model, computed on the device in float64: K[9] the source camera, dist[8] = k1, k2, p1, p2,
+ * k3, k4, k5, k6 (OpenCV's order), M[9] = (K_new * R)^-1 inverted by the caller.  With (X, Y, Wd) = M (u, v, 1),
+ * x = X / Wd, y = Y / Wd, r2 = x^2 + y^2 and kr = (1 + k1 r2 + k2 r2^2 + k3 r2^3) / (1 + k4 r2 + k5 r2^2 + k6 r2^3):
+ * mu = fx (x kr + 2 p1 x y + p2 (r2 + 2 x^2)) + cx, mv = fy (y kr + p1 (r2 + 2 y^2) + 2 p2 x y) + cy, in the
+ * operation order DESIGN.md states; q = rint(32 m) where both are inside (-65536, 65536), else both OUTSIDE.
+ * Non-finite entries are YV_ERR_INVALID.  Like yv_rectify_set_map it waits for the device (a run in flight reads
+ * the map). */
+int yv_rectify_set_model(yv_rectify* r, int map, const double K[9], const double dist[8], const double M[9]);
+/* a map of the caller's: any int32 values (host, [dst_H][dst_W][2]) */
+int yv_rectify_set_map(yv_rectify* r, int map, const int32_t* map_q5);
+/* the map as set, or as the model gave it (host, blocking); YV_ERR_INVALID for a map never set */
+int yv_rectify_map_read(yv_rectify* r, int map, int32_t* map_q5);
+/* image i: source at d_src + i * src_pitch (rows src_stride apart), destination at d_dst + i * dst_pitch, through map
+ * i % n_maps (left, right per frame: the layout yv_seq_upload_gpu writes); asynchronous on stream (NULL: the
+ * context's).  No byte outside the sources' rows is read, none outside the destinations' dst_W-byte rows written.
+ * YV_ERR_INVALID when a map it would use was never set; n_images == 0 does nothing. */
+int yv_rectify_run(yv_rectify* r, const uint8_t* d_src, int src_stride, int64_t src_pitch, uint8_t* d_dst,
+                   int dst_stride, int64_t dst_pitch, int n_images, void* stream);
+/* host-pointer form for one image and one map of the caller's (the reference's declared and never defined
+ * Image::unDistort, include/Image.hpp:25); blocking */
+int yv_rectify_image(struct yv_ctx* ctx, const uint8_t* src, int src_H, int src_W, int src_stride,
+                     const int32_t* map_q5, uint8_t* dst, int dst_H, int dst_W, int dst_stride);
+/* for tests and measurements: how many of a set map's 16 x 256 destination tiles take the LDS-staged kernel and how
+ * many the direct one; on != 0 sends every tile of the following runs through the direct kernel */
+int yv_rectify_debug_tiles(yv_rectify* r, int map, int32_t* n_lds, int32_t* n_direct);
+int yv_rectify_debug_force_direct(yv_rectify* r, int on);
 
 /* The writer side, for test sequences (the reference only reads PNGs): an 8-bit grey image to a PNG file, every row
  * Sub-filtered and deflated at level 1 with Z_RLE, as cv::imwrite writes PNGs (the reference's tests/epilines.png:

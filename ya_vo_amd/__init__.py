@@ -211,6 +211,15 @@ IO_SIGNATURES = {
     "yv_seq_upload_gpu_frames": (_I, [_P, _P, _P, _I, _P, ctypes.c_int64, _I, _P]),
     "yv_pngdec_status": (_I, [_P, _P, ctypes.POINTER(_I)]),
     "yv_pngdec_set_checks": (_I, [_P, _I, _I]),
+    "yv_rectify_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
+    "yv_rectify_destroy": (None, [_P]),
+    "yv_rectify_set_model": (_I, [_P, _I, _P, _P, _P]),
+    "yv_rectify_set_map": (_I, [_P, _I, _P]),
+    "yv_rectify_map_read": (_I, [_P, _I, _P]),
+    "yv_rectify_run": (_I, [_P, _P, _I, ctypes.c_int64, _P, _I, ctypes.c_int64, _I, _P]),
+    "yv_rectify_image": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _I, _I]),
+    "yv_rectify_debug_tiles": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "yv_rectify_debug_force_direct": (_I, [_P, _I]),
     "yv_write_kitti_poses": (_I, [ctypes.c_char_p, _P, _I]),
     "yv_read_kitti_poses": (_I, [ctypes.c_char_p, _P, _I, ctypes.POINTER(_I)]),
 }

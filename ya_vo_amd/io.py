@@ -171,3 +171,93 @@ class PngDecoder:
         if self.handle:
             self.lib.yv_pngdec_destroy(self.handle)
             self.handle = None
+
+
+YV_RECTIFY_OUTSIDE = -2 ** 31
+
+
+def rectify_matrix(K_new, R) -> np.ndarray:
+    """inv(K_new @ R) flattened: the M of Rectifier.set_model (cv::initUndistortRectifyMap's iR)."""
+    K_new, R = np.asarray(K_new, np.float64).reshape(3, 3), np.asarray(R, np.float64).reshape(3, 3)
+    return np.linalg.inv(K_new @ R).reshape(9)
+
+
+class Rectifier:
+    """Undistortion + rectification of device images (yv_rectify_*): n_maps maps (2: left, right) from src_hw to
+    dst_hw, int32 [H, W, 2] = (source column, source row) in 1/32 pixel, YV_RECTIFY_OUTSIDE = no source."""
+
+    _close_rank = 2
+
+    def __init__(self, ctx, n_maps: int, src_hw, dst_hw):
+        self.ctx, self.lib = ctx, _lib()
+        self.n_maps = int(n_maps)
+        self.src_hw, self.dst_hw = (int(src_hw[0]), int(src_hw[1])), (int(dst_hw[0]), int(dst_hw[1]))
+        h = ctypes.c_void_p()
+        _check(self.lib.yv_rectify_create(ctx.handle, self.n_maps, *self.src_hw, *self.dst_hw, ctypes.byref(h)),
+               "yv_rectify_create")
+        self.handle = h
+        ctx._own(self)
+
+    def set_model(self, m: int, K, dist, M) -> None:
+        """The map of a camera: K the source camera, dist = (k1, k2, p1, p2, k3, k4, k5, k6) (shorter: zeros appended),
+        M = rectify_matrix(K_new, R)."""
+        K = np.ascontiguousarray(K, np.float64).reshape(9)
+        d = np.zeros(8, np.float64)
+        dist = np.asarray(dist, np.float64).reshape(-1)
+        d[:len(dist)] = dist
+        M = np.ascontiguousarray(M, np.float64).reshape(9)
+        _check(self.lib.yv_rectify_set_model(self.handle, int(m), K.ctypes.data, d.ctypes.data, M.ctypes.data),
+               "yv_rectify_set_model")
+
+    def set_map(self, m: int, map_q5) -> None:
+        q = np.ascontiguousarray(map_q5, np.int32)
+        if q.shape != (*self.dst_hw, 2):
+            raise ValueError(f"map_q5 must be [{self.dst_hw[0]}, {self.dst_hw[1]}, 2]")
+        _check(self.lib.yv_rectify_set_map(self.handle, int(m), q.ctypes.data), "yv_rectify_set_map")
+
+    def map(self, m: int) -> np.ndarray:
+        q = np.zeros((*self.dst_hw, 2), np.int32)
+        _check(self.lib.yv_rectify_map_read(self.handle, int(m), q.ctypes.data), "yv_rectify_map_read")
+        return q
+
+    def run(self, d_src: int, d_dst: int, n: int, src_stride: int = 0, src_pitch: int = 0, dst_stride: int = 0,
+            dst_pitch: int = 0, stream: int = 0) -> None:
+        """n device images (image i through map i % n_maps); strides and pitches default to packed images."""
+        ss, ds = src_stride or self.src_hw[1], dst_stride or self.dst_hw[1]
+        sp, dp = src_pitch or self.src_hw[0] * ss, dst_pitch or self.dst_hw[0] * ds
+        _check(self.lib.yv_rectify_run(self.handle, ctypes.c_void_p(d_src), ss, sp, ctypes.c_void_p(d_dst), ds, dp,
+                                       int(n), ctypes.c_void_p(stream) if stream else None), "yv_rectify_run")
+
+    def tiles(self, m: int):
+        """(tiles of map m on the LDS-staged kernel, tiles on the direct kernel) (yv_rectify_debug_tiles)."""
+        a, b = ctypes.c_int32(), ctypes.c_int32()
+        _check(self.lib.yv_rectify_debug_tiles(self.handle, int(m), ctypes.byref(a), ctypes.byref(b)),
+               "yv_rectify_debug_tiles")
+        return a.value, b.value
+
+    def force_direct(self, on: bool = True) -> None:
+        _check(self.lib.yv_rectify_debug_force_direct(self.handle, int(bool(on))), "yv_rectify_debug_force_direct")
+
+    def close(self) -> None:
+        if self.handle:
+            self.lib.yv_rectify_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def rectify_image(ctx, src, map_q5, dst_hw=None) -> np.ndarray:
+    """One host image through one map (yv_rectify_image, cv::remap INTER_LINEAR BORDER_CONSTANT 0) -> uint8 [H, W]."""
+    src = np.ascontiguousarray(src, np.uint8)
+    q = np.ascontiguousarray(map_q5, np.int32)
+    H, W = (int(dst_hw[0]), int(dst_hw[1])) if dst_hw is not None else q.shape[:2]
+    if q.shape != (H, W, 2):
+        raise ValueError(f"map_q5 must be [{H}, {W}, 2]")
+    dst = np.zeros((H, W), np.uint8)
+    _check(_lib().yv_rectify_image(ctx.handle, src.ctypes.data, src.shape[0], src.shape[1], src.shape[1],
+                                   q.ctypes.data, dst.ctypes.data, H, W, W), "yv_rectify_image")
+    return dst
