@@ -562,6 +562,40 @@ def test_lk_mode_uses_the_refined_stereo_points(ctx, oracle, frames, d_frames):
     b.close()
 
 
+def test_lk_mode_under_the_match_filter_and_the_refinement(ctx, oracle):
+    """LK mode with the 2-NN filter and the refinement both on (the 200 x 320, seed 78 frames of
+    test_under_the_match_filter_and_gates): frame k-1's map points are the stereo matches that removeOutliers and the
+    filter keep, triangulated from the refined columns."""
+    h, w = 200, 320
+    fr = _frames(h, w, seed=78)
+    d = _to_device(fr)
+    d_prior, d_pose = _pose_buffers(1)
+    b = yv.Batch(ctx, 4, h, w, K, 2)
+    b.set_pairs([(0, 1), (2, 3)])
+    b.set_track_lk(2)
+    b.set_tracks([(0, 2)], scene.K_KITTI, T_RIGHT)  # {stereo pair of frame 0, image L1}
+    b.set_match_filter(ratio=(4, 5), mutual=True)
+    b.set_stereo_subpix([0], 5, 3)
+    b.run(d.data_ptr(), 4, w, h * w, THR)
+    b.track(d_prior.data_ptr(), d_pose.data_ptr())
+    snap = _snapshot(ctx, b, 4, 2, 1, h, w)
+    pose = d_pose.cpu().numpy()
+    arr = _subpix_arrays(ctx, b, 2)
+    keep = ctx.download(b.match2_view().keep, np.uint8, K).astype(bool)
+    nq = len(snap["keypoints0"])
+    dj = snap["match_dj0"]
+    passed = (dj[:, 0] < snap["match_lim"][0]) & (dj[:, 1] >= 0)
+    j = snap["edge_query0"]
+    assert len(j) >= 10 and (passed & ~keep[:nq]).sum() >= 1  # kept by removeOutliers, dropped by the filter
+    assert (passed[j] & keep[j]).all()
+    X, ok = ssr.triangulate_refined(oracle, IDENTITY, T_RIGHT, scene.K_KITTI, _stereo_records(snap, 0, 0, 1, j),
+                                    arr[0][0][j])
+    assert ok.all() and snap["edge_X0"].tobytes() == X.tobytes()
+    T, out, inl = oracle.pose_lm(snap["edge_X0"], snap["edge_uv0"], scene.K_KITTI, IDENTITY, yv.track_lm_sum_mode(1))
+    assert pose[0].tobytes() == T.tobytes() and snap["track_inliers"][0] == inl
+    b.close()
+
+
 @pytest.mark.parametrize("overlap", [0, 1])
 def test_through_track_map(ctx, oracle, frames, d_frames, off_on, overlap):
     """yv_batch_track_map (with the asynchronous edge build under overlap): the refined edges, and the map block the

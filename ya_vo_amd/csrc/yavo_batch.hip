@@ -1,27 +1,14 @@
-// yavo_batch.hip -- the batched device pipeline of the C ABI (include/yavo/yavo.h): yv_batch_* and the buffers,
-// the match stage and the opt-in stages behind it, which the host-pointer front end (yavo_api.hip) runs on its
-// single-image workspace as well.  Host code only; kernels live in yavo_kernels.hip and its siblings.
+// yavo_batch.hip -- the batched device pipeline of the C ABI (include/yavo/yavo.h): yv_batch_* up to the run and the
+// view, the buffers, the match stage and the opt-in stages behind it, which the host-pointer front end (yavo_api.hip)
+// runs on its single-image workspace as well.  The tracks (yv_batch_set_tracks, yv_batch_track and what follows a run's
+// matches) are in yavo_batch_track.hip.  Host code only; kernels live in yavo_kernels.hip and its siblings.
 #include "yavo_host.h"
-
-#include <cstdlib>
-
-#include "../../include/yavo/yavo_map.h"
 
 using namespace yavo;
 
 namespace {
 
-constexpr int kEvPerRun = 9;
 constexpr int kMaxTimedRuns = 4096;
-
-// the next writer of what an asynchronous edge build reads (keypoint counts, keypoints, match lists, pairs,
-// tracks) is ordered after it on stream s
-int join_build(yv_batch* b, hipStream_t s) {
-    if (!b->build_pending) return YV_OK;
-    YV_HIP(hipStreamWaitEvent(s, b->ev_built, 0));
-    b->build_pending = false;
-    return YV_OK;
-}
 
 // the swapped pair list of the reverse match
 int upload_pairs_rev(yv_batch* b) {
@@ -77,13 +64,6 @@ int ensure_subpix(yv_batch* b) {
     }
     b->subpix_alloc = true;
     return YV_OK;
-}
-
-// what the track builders read of the refinement (nullptr while it is off: the unrefined kernels)
-const yavo::SubpixUse* subpix_use(const yv_batch* b, yavo::SubpixUse* u) {
-    if (!b->subpix_on) return nullptr;
-    *u = {b->subpix_dcol, b->subpix_status, (b->subpix_flags & YV_SUBPIX_DROP_EDGE) != 0};
-    return u;
 }
 
 }  // namespace
@@ -523,11 +503,6 @@ int yv_batch_stage_times(yv_batch* b, float* ms, int* n_runs) {
     return YV_OK;
 }
 
-namespace {
-int launch_deferred_after(yv_batch* b, hipStream_t s);
-int flush_deferred(yv_batch* b);
-}  // namespace
-
 int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride, int64_t image_pitch, int match_thr,
                  int carry_from, void* stream) {
     if (!b || !d_images || n_images <= 0 || n_images > b->max_images || stride < b->W ||
@@ -638,367 +613,13 @@ int yv_batch_view_get(yv_batch* b, yv_batch_view* v) {
     v->match_dj = reinterpret_cast<const int32_t*>(b->match_dj);
     v->match_lim = b->match_lim;
     v->n_tracks = b->n_tracks;
-    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp, k = (size_t)b->tbuf;
-    v->edge_count = b->edge_count ? b->edge_count + k * nt : nullptr;
-    v->edge_X = b->edge_X ? b->edge_X + k * nt * nk * 3 : nullptr;
-    v->edge_uv = b->edge_uv ? b->edge_uv + k * nt * nk * 2 : nullptr;
-    v->edge_query = b->edge_query ? b->edge_query + k * nt * nk : nullptr;
-    v->edge_outlier = b->edge_outlier ? b->edge_outlier + k * nt * nk : nullptr;
-    v->track_inliers = b->track_inliers ? b->track_inliers + k * nt : nullptr;
-    return YV_OK;
-}
-
-int yv_batch_set_tracks(yv_batch* b, const int32_t* tracks, int n_tracks, const double K[9], const double T_right[7]) {
-    if (!b || n_tracks < 0 || (n_tracks > 0 && (!tracks || !K || !T_right))) return YV_ERR_INVALID;
-    for (int t = 0; t < n_tracks; ++t) {
-        const int sp = tracks[2 * t], tp = tracks[2 * t + 1];
-        if (sp < 0 || sp >= b->n_pairs) return YV_ERR_INVALID;
-        if (b->lk_step > 0) {
-            // LK mode: {stereo pair of frame k-1, image of frame k}, both LK images (multiples of the step)
-            const int prev = b->h_pairs[2 * sp];
-            if (prev % b->lk_step || prev >= b->max_images || tp < 0 || tp >= b->max_images || tp % b->lk_step)
-                return YV_ERR_INVALID;
-        } else {
-            if (tp < 0 || tp >= b->n_pairs) return YV_ERR_INVALID;
-            if (b->h_pairs[2 * sp] != b->h_pairs[2 * tp + 1]) return YV_ERR_INVALID;  // stereo query = temporal train
-        }
-    }
-    for (int i = 0; i < 9 && n_tracks > 0; ++i)
-        if (!std::isfinite(K[i])) return YV_ERR_INVALID;
-    if (n_tracks > 0 && !finite_pose(T_right)) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    hipStream_t s = b->ctx->stream;
-    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // a build in flight reads tracks / K
-    b->build_pending = false;
-    if (b->side) YV_HIP(hipStreamSynchronize(b->side));  // an LM in flight reads tracks / K
-    if (n_tracks > b->max_tracks) {
-        YV_HIP(hipStreamSynchronize(s));
-        if (b->side) YV_HIP(hipStreamSynchronize(b->side));
-        b->track_mem.clear();
-        b->max_tracks = 0;
-        b->n_tracks = 0;
-        const size_t nt = (size_t)n_tracks, nk = (size_t)b->max_kp;
-        int rc = YV_OK;
-        rc |= b->track_mem.alloc(&b->tracks, 2 * nt);
-        rc |= b->track_mem.alloc(&b->track_K, 9 * nt);
-        rc |= b->track_mem.alloc(&b->T_right, 7);
-        rc |= b->track_mem.alloc(&b->edge_X, kEdgeBufs * 3 * nt * nk);
-        rc |= b->track_mem.alloc(&b->edge_uv, kEdgeBufs * 2 * nt * nk);
-        rc |= b->track_mem.alloc(&b->edge_query, kEdgeBufs * nt * nk);
-        rc |= b->track_mem.alloc(&b->edge_count, kEdgeBufs * nt);
-        rc |= b->track_mem.alloc(&b->edge_outlier, kEdgeBufs * nt * nk);
-        rc |= b->track_mem.alloc(&b->track_inliers, kEdgeBufs * nt);
-        rc |= b->track_mem.alloc(&b->lk_sp, nt);
-        rc |= b->track_mem.alloc(&b->lk_pairs, 2 * nt);
-        rc |= b->track_mem.alloc(&b->lk_X, 2 * 3 * nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_pts, 2 * 2 * nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_next, 2 * nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_err, nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_status, nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_q, 2 * nt * nk);
-        rc |= b->track_mem.alloc(&b->lk_count, 2 * nt);
-        b->lk_ev_pending[0] = b->lk_ev_pending[1] = false;
-        if (rc != YV_OK) return YV_ERR_HIP;
-        b->max_tracks = n_tracks;
-    }
-    if (n_tracks > 0) {
-        std::vector<double> Ks(9 * (size_t)n_tracks);
-        for (int t = 0; t < n_tracks; ++t) std::memcpy(&Ks[9 * (size_t)t], K, 9 * sizeof(double));
-        YV_HIP(hipMemcpyAsync(b->tracks, tracks, 2 * sizeof(int32_t) * (size_t)n_tracks, hipMemcpyHostToDevice, s));
-        YV_HIP(hipMemcpyAsync(b->track_K, Ks.data(), Ks.size() * sizeof(double), hipMemcpyHostToDevice, s));
-        YV_HIP(hipMemcpyAsync(b->T_right, T_right, 7 * sizeof(double), hipMemcpyHostToDevice, s));
-        YV_HIP(hipMemsetAsync(b->edge_count, 0, kEdgeBufs * sizeof(int32_t) * (size_t)b->max_tracks, s));
-        if (b->lk_step > 0) {
-            std::vector<int32_t> sp(n_tracks), lp(2 * (size_t)n_tracks);
-            for (int t = 0; t < n_tracks; ++t) {
-                sp[t] = tracks[2 * t];
-                lp[2 * t] = b->h_pairs[2 * sp[t]] / b->lk_step;
-                lp[2 * t + 1] = tracks[2 * t + 1] / b->lk_step;
-            }
-            YV_HIP(hipMemcpyAsync(b->lk_sp, sp.data(), sizeof(int32_t) * sp.size(), hipMemcpyHostToDevice, s));
-            YV_HIP(hipMemcpyAsync(b->lk_pairs, lp.data(), sizeof(int32_t) * lp.size(), hipMemcpyHostToDevice, s));
-        }
-        YV_HIP(hipStreamSynchronize(s));
-    }
-    b->n_tracks = n_tracks;
-    return YV_OK;
-}
-
-namespace {
-
-struct MapArgs {
-    int64_t first_frame;
-    int kf_every, max_kf;
-    void* block;
-};
-
-int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream, const MapArgs* map);
-
-// The pose LM (and the map block) of one track. Overlap: on the side stream after the edge build (ev_edges[k]);
-// otherwise on `s`, in order.
-int launch_lm(yv_batch* b, const yv_batch::DeferredLM& L, hipStream_t s) {
-    const int k = L.k;
-    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
-    double* eX = b->edge_X + k * nt * nk * 3;
-    double* euv = b->edge_uv + k * nt * nk * 2;
-    int32_t* ec = b->edge_count + k * nt;
-    uint8_t* eo = b->edge_outlier + k * nt * nk;
-    int32_t* inl = b->track_inliers + k * nt;
-    hipStream_t ls = s;
-    if (b->overlap) {
-        // the LM reads only this track's edge buffer, priors and poses: it runs on the side stream beside the
-        // next batch's image kernels (which overwrite keypoints / matches, already consumed by the build)
-        YV_HIP(hipStreamWaitEvent(b->side, b->ev_edges[k], 0));
-        ls = b->side;
-    }
-    if (L.ev) YV_HIP(hipEventRecord(L.ev[7], ls));
-    yavo::launch_track_pose(b->n_tracks, ec, b->max_kp, eX, euv, b->track_K, L.priors, L.poses, eo, inl, ls);
-    if (L.ev) {
-        YV_HIP(hipEventRecord(L.ev[8], ls));
-        b->tracked[L.run] = 1;
-    }
-    if (L.has_map) {
-        // the chunk's map block, after the LM on its stream: the build that next rewrites this edge buffer waits
-        // for ev_lm[k], recorded below, so it also waits for these reads. The block itself is rewritten only
-        // after its last reader released it (the all-gather of the previous chunk, yv_batch_map_release).
-        if (b->map_release_pending) {
-            YV_HIP(hipStreamWaitEvent(ls, b->ev_map_release, 0));
-            b->map_release_pending = false;
-        }
-        yavo::launch_map_chunk(L.poses, b->n_tracks, L.first_frame, L.kf_every, ec, eX, eo, b->max_kp, L.max_kf,
-                               L.block, ls);
-        if (!b->ev_map) YV_HIP(b->mem.event(&b->ev_map));
-        YV_HIP(hipEventRecord(b->ev_map, ls));
-        b->map_written = true;
-    }
-    if (b->overlap) {
-        YV_HIP(hipEventRecord(b->ev_lm[k], ls));
-        b->lm_pending[k] = true;
-    }
-    return YV_OK;
-}
-
-// The deferred LM of the previous track, ordered after the work issued on s so far (the stage it waits for).
-int launch_deferred_after(yv_batch* b, hipStream_t s) {
-    if (!b->deferred.active) return YV_OK;
-    if (!b->ev_defer) YV_HIP(b->mem.event(&b->ev_defer));
-    YV_HIP(hipEventRecord(b->ev_defer, s));
-    YV_HIP(hipStreamWaitEvent(b->side, b->ev_defer, 0));
-    b->deferred.active = false;
-    return launch_lm(b, b->deferred, s) == YV_OK ? YV_OK : YV_ERR_HIP;
-}
-
-// Launch a deferred LM now (its inputs are complete once ev_edges was recorded).
-int flush_deferred(yv_batch* b) {
-    if (!b->deferred.active) return YV_OK;
-    b->deferred.active = false;
-    return launch_lm(b, b->deferred, b->ctx->stream);
-}
-
-}  // namespace
-
-int yv_batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream) {
-    return batch_track(b, d_priors, d_poses, stream, nullptr);
-}
-
-int yv_batch_track_map(yv_batch* b, const double* d_priors, double* d_poses, int64_t first_frame, int kf_every,
-                       void* d_block, int max_kf, void* stream) {
-    if (!b || !d_block || kf_every < 1 || max_kf < 1 || first_frame < 0) return YV_ERR_INVALID;
-    const MapArgs m{first_frame, kf_every, max_kf, d_block};
-    return batch_track(b, d_priors, d_poses, stream, &m);
-}
-
-int yv_batch_map_wait(yv_batch* b, void* stream) {
-    if (!b || !stream) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;  // the block is written after the LM
-    if (!b->map_written) return YV_OK;
-    YV_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), b->ev_map, 0));
-    return YV_OK;
-}
-
-int yv_batch_map_release(yv_batch* b, void* stream) {
-    if (!b || !stream) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    if (!b->ev_map_release) YV_HIP(b->mem.event(&b->ev_map_release));
-    YV_HIP(hipEventRecord(b->ev_map_release, reinterpret_cast<hipStream_t>(stream)));
-    b->map_release_pending = true;
-    return YV_OK;
-}
-
-namespace {
-
-int batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* stream, const MapArgs* map) {
-    if (!b || (b->n_tracks > 0 && (!d_priors || !d_poses))) return YV_ERR_INVALID;
-    if (b->n_tracks == 0) return YV_OK;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : b->ctx->stream;
-    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;  // two tracks without a run between them
-    const int k = b->track_calls++ % kEdgeBufs;
-    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
-    double* eX = b->edge_X + k * nt * nk * 3;
-    double* euv = b->edge_uv + k * nt * nk * 2;
-    int32_t* eq = b->edge_query + k * nt * nk;
-    int32_t* ec = b->edge_count + k * nt;
-    const int run = b->last_run;
-    const bool timed = b->timing == 1 && run >= 0 && !b->tracked[run];
-    hipEvent_t* ev = timed ? &b->events[(size_t)run * kEvPerRun] : nullptr;
-    const hipStream_t s_run = s;
-    yavo::SubpixUse sub_use{};
-    double* lkX = nullptr;
-    float* lkP = nullptr;
-    int32_t *lkQ = nullptr, *lkC = nullptr;
-    int lk_j = 0;
-    if (b->lk_step > 0) {
-        // LK: frame k-1's stereo map points from this run's keypoints / matches, on the run's stream (the next run
-        // rewrites them), into the point set the LK stage two tracks ago has finished reading
-        if (!b->run_images || b->run_n < b->lk_step) return YV_ERR_INVALID;
-        lk_j = b->lk_set;
-        b->lk_set ^= 1;
-        lkX = b->lk_X + (size_t)lk_j * nt * nk * 3;
-        lkP = b->lk_pts + (size_t)lk_j * nt * nk * 2;
-        lkQ = b->lk_q + (size_t)lk_j * nt * nk;
-        lkC = b->lk_count + (size_t)lk_j * nt;
-        if (b->lk_ev_pending[lk_j]) YV_HIP(hipStreamWaitEvent(s_run, b->ev_lk[lk_j], 0));
-        b->lk_ev_pending[lk_j] = false;
-        yavo::launch_stereo_points(b->lk_sp, b->n_tracks, b->pairs, b->keypoints, b->kp_count, b->match_dj,
-                                   b->match_lim, b->max_kp, b->track_K, b->T_right, lkX, lkP, lkQ, lkC, s_run,
-                                   b->run_flags ? b->keep : nullptr, subpix_use(b, &sub_use));
-    }
-    const int32_t* build_counts = b->kp_count;
-    if (b->overlap && b->build_async) {
-        // the build (match: edges from the run's matches; LK: pyramids, flow, edges) waits for the run on s and
-        // leaves s free for the next run's detect; the match build reads a copy of the keypoint counts
-        if (b->lk_step == 0) {
-            if (!b->counts_copied)
-                YV_HIP(hipMemcpyAsync(b->kp_count_build, b->kp_count, sizeof(int32_t) * (size_t)b->nslots,
-                                      hipMemcpyDeviceToDevice, s_run));
-            build_counts = b->kp_count_build;
-        }
-        YV_HIP(hipEventRecord(b->ev_fin, s_run));
-        YV_HIP(hipStreamWaitEvent(b->bstream, b->ev_fin, 0));
-        s = b->bstream;
-    }
-    // buffer k was last read by the LM kEdgeBufs tracks ago (side stream): the build must not overwrite it early
-    if (b->lm_pending[k]) YV_HIP(hipStreamWaitEvent(s, b->ev_lm[k], 0));
-    if (timed) YV_HIP(hipEventRecord(ev[6], s));
-    if (b->lk_step > 0) {
-        // trackLastFrame: frame k-1's stereo map points -> calcOpticalFlowPyrLK into frame k -> edges
-        const int n_lk = (b->run_n + b->lk_step - 1) / b->lk_step;
-        int rc = yv_lk_build(b->lk, b->run_images, n_lk, b->run_stride, b->run_pitch * b->lk_step, s);
-        if (rc != YV_OK) return rc;
-        rc = yv_lk_track_batch(b->lk, b->lk_pairs, b->n_tracks, lkP, lkC, b->max_kp, b->lk_max_count, b->lk_eps,
-                               b->lk_min_eig, b->lk_next, b->lk_status, b->lk_err, s);
-        if (rc != YV_OK) return rc;
-        yavo::launch_lk_edges(b->n_tracks, lkX, b->lk_next, b->lk_status, lkQ, lkC, b->max_kp, eX, euv, eq, ec, s);
-        if (s != s_run) {
-            if (!b->ev_lk[lk_j]) YV_HIP(b->mem.event(&b->ev_lk[lk_j]));
-            YV_HIP(hipEventRecord(b->ev_lk[lk_j], s));
-            b->lk_ev_pending[lk_j] = true;
-        }
-    } else {
-        yavo::launch_track_build(b->tracks, b->n_tracks, b->pairs, b->keypoints, build_counts, b->match_dj,
-                                 b->match_lim, b->max_kp, b->track_K, b->T_right, eX, euv, eq, ec, s,
-                                 b->run_flags ? b->keep : nullptr, subpix_use(b, &sub_use));
-    }
-    if (b->overlap) YV_HIP(hipEventRecord(b->ev_edges[k], s));
-    if (s != s_run && b->lk_step == 0) {  // (the LK stage reads nothing the next run writes: no join)
-        YV_HIP(hipEventRecord(b->ev_built, s));
-        b->build_pending = true;
-    }
-    yv_batch::DeferredLM L;
-    L.active = true;
-    L.k = k;
-    L.run = timed ? run : -1;
-    L.priors = d_priors;
-    L.poses = d_poses;
-    L.ev = ev;
-    if (map) {
-        L.has_map = true;
-        L.first_frame = map->first_frame;
-        L.kf_every = map->kf_every;
-        L.max_kf = map->max_kf;
-        L.block = map->block;
-    }
-    b->tbuf = k;
-    if (b->overlap_mode >= 2) {
-        // launched by the next yv_batch_run after its detect (2) / describe (3) stage, or by a flush
-        b->deferred = L;
-        return check_launch();
-    }
-    const int rc = launch_lm(b, L, s);
-    if (rc != YV_OK) return rc;
-    return check_launch();
-}
-
-}  // namespace
-
-int yv_batch_set_track_overlap(yv_batch* b, int on) {
-    if (!b || on < 0 || on > 4) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
-    if (on && !b->side) {
-        // lowest priority: the LM fills the CUs the next batch's detect / describe / match leave idle
-        int least = 0, greatest = 0;
-        YV_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        YV_HIP(hipStreamCreateWithPriority(&b->side, hipStreamNonBlocking, least));
-        b->mem.adopt(b->side);
-        for (int k = 0; k < kEdgeBufs; ++k) {
-            YV_HIP(b->mem.event(&b->ev_edges[k]));
-            YV_HIP(b->mem.event(&b->ev_lm[k]));
-        }
-        // the build stream at the default priority (the highest and the lowest measured the same)
-        YV_HIP(hipStreamCreateWithFlags(&b->bstream, hipStreamNonBlocking));
-        b->mem.adopt(b->bstream);
-        YV_HIP(b->mem.event(&b->ev_fin));
-        YV_HIP(b->mem.event(&b->ev_built));
-    }
-    if (!on && b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
-    if (!on) b->build_pending = false;
-    {
-        const char* e = std::getenv("YAVO_BUILD_ASYNC");
-        b->build_async = on != 0 && !(e && e[0] == '0');
-    }
-    if (!on && b->side) YV_HIP(hipStreamSynchronize(b->side));
-    b->overlap = on != 0;
-    b->overlap_mode = on;
-    return YV_OK;
-}
-
-int yv_batch_track_sync(yv_batch* b) {
-    if (!b) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
-    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
-    if (b->side) YV_HIP(hipStreamSynchronize(b->side));
-    return YV_OK;
-}
-
-int yv_batch_set_track_lk(yv_batch* b, int image_step, int win, int max_level, int max_count, double eps,
-                          double min_eig) {
-    if (!b || image_step < 0 || (image_step > 0 && (win < 3 || win > 22 || max_level < 0))) return YV_ERR_INVALID;
-    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
-    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
-    if (b->side) YV_HIP(hipStreamSynchronize(b->side));
-    if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // an edge build in flight (as its siblings drain)
-    b->build_pending = false;
-    YV_HIP(hipStreamSynchronize(b->ctx->stream));
-    if (b->lk) {
-        yv_lk_destroy(b->lk);
-        b->lk = nullptr;
-    }
-    b->lk_step = image_step;
-    b->n_tracks = 0;  // tracks change meaning with the mode: set them again
-    if (image_step == 0) return YV_OK;
-    const int slots = (b->max_images + image_step - 1) / image_step;
-    const int rc = yv_lk_create(b->ctx, slots, b->H, b->W, win, max_level, &b->lk);
-    if (rc != YV_OK) {
-        b->lk_step = 0;
-        return rc;
-    }
-    b->lk_max_count = max_count;
-    b->lk_eps = eps;
-    b->lk_min_eig = min_eig;
+    const EdgeSlice e = edge_slice(b, b->tbuf);
+    v->edge_count = e.count;
+    v->edge_X = e.X;
+    v->edge_uv = e.uv;
+    v->edge_query = e.query;
+    v->edge_outlier = e.outlier;
+    v->track_inliers = e.inliers;
     return YV_OK;
 }
 

@@ -12,6 +12,8 @@
 //                        fixed-order tree reductions in LDS, the 6x6 LDLT + LM control on lane 0
 //   pose_gn_kernel       bundleAdjustmentGaussNewton                      src/test.cc:172-244
 //
+// The triangulation of one match, the workgroup scan and kNT are in yavo_geom_dev.h, shared with the track kernels
+// (yavo_track.hip), which turn a run's matches into the pose LM's edges.
 // Every floating-point expression is written in the reference's operation order and the file is built
 // with -ffp-contract=off, so each kernel matches oracle/yavo_oracle_geom.c bit for bit (sums over edges
 // in the oracle's sum_mode 1 = this file's tree order).
@@ -23,6 +25,7 @@
 
 #include "yavo_internal.h"
 #include "yavo_cvsvd.h"
+#include "yavo_geom_dev.h"
 #include "yavo_se3.h"
 #include "yavo_xlane.h"
 
@@ -38,12 +41,9 @@ using se3::k_sin;
 using se3::mm3;
 using se3::quat_mul;
 using se3::quat_rotate;
-using se3::quat_to_R;
 using se3::se3_act;
 using se3::se3_exp;
 using se3::se3_mul;
-
-constexpr int kNT = 256;          // threads per workgroup of the reduction kernels
 
 // YAVO_LM_PROFILE builds (tools/lm_profile.py) time the pose-LM phases with the shader clock on lane 0
 #ifdef YAVO_LM_PROFILE
@@ -57,28 +57,6 @@ __device__ unsigned long long g_lm_prof[1024][10];
 #define LMP_STORE() do {} while (0)
 #endif
 constexpr int kMaxEdges = 4096;   // edges per pose problem held in LDS
-
-// exclusive scan over an NT-thread block; s_tmp >= NT/64 ints
-template <int NT = kNT>
-__device__ int block_excl_scan_geom(int v, int* s_tmp, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) s_tmp[wave] = incl;
-    __syncthreads();
-    int base = 0, tot = 0;
-    for (int w = 0; w < NT / 64; ++w) {
-        if (w < wave) base += s_tmp[w];
-        tot += s_tmp[w];
-    }
-    __syncthreads();
-    if (total) *total = tot;
-    return base + incl - v;
-}
 
 // OpenCV JacobiSVDImpl_<double>, cv::RNG, hypot: yavo_cvsvd.h
 
@@ -400,194 +378,8 @@ __global__ __launch_bounds__(64) void f_select_kernel(const int32_t* __restrict_
 // Sophus SE3 (pose = {qx, qy, qz, qw, tx, ty, tz}): yavo_se3.h
 
 // ------------------------------------------------------------------------------------------------
-// triangulation (Eigen JacobiSVD 4x4, registers) and world2Camera
+// triangulation (triangulate_px: yavo_geom_dev.h) and world2Camera
 // ------------------------------------------------------------------------------------------------
-struct JRot {
-    double c, s;
-};
-
-__device__ __forceinline__ JRot make_jacobi(double x, double y, double z) {
-    JRot r;
-    double deno = 2 * fabs(y);
-    if (deno < DBL_MIN) {
-        r.c = 1; r.s = 0;
-        return r;
-    }
-    double tau = (x - z) / deno;
-    double w = sqrt(tau * tau + 1);
-    double t = tau > 0 ? 1 / (tau + w) : 1 / (tau - w);
-    double sign_t = t > 0 ? 1 : -1;
-    double nn = 1 / sqrt(t * t + 1);
-    // Eigen's y / |y|: exactly +-1 here (2|y| >= DBL_MIN, and the inputs are finite and scaled to <= 1), so the
-    // sign is taken instead of an FP64 division (one of the seven per rotation); the products are unchanged
-    r.s = -sign_t * copysign(1.0, y) * fabs(t) * nn;
-    r.c = nn;
-    return r;
-}
-
-// JacobiSVD<MatrixXd>(A 4x4 column-major): sv descending, V column-major.  false on non-finite input.
-__device__ bool eigen_jacobi_svd4(const double (&Ain)[16], double (&sv)[4], double (&V)[16]) {
-    constexpr int n = 4;
-    double Wk[16];
-    double scale = 0;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        double a = fabs(Ain[i]);
-        if (a != a) return false;
-        if (a > scale) scale = a;
-    }
-    if (!isfinite(scale)) return false;
-    if (scale == 0) scale = 1;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) Wk[i] = Ain[i] / scale;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    const double considerAsZero = DBL_MIN, precision = 2 * DBL_EPSILON;
-    double maxDiag = 0;
-#pragma unroll
-    for (int i = 0; i < n; ++i) {
-        double a = fabs(Wk[i + i * n]);
-        if (a > maxDiag) maxDiag = a;
-    }
-    bool finished = false;
-    int guard = 0;
-    while (!finished && guard < 10000) {
-        finished = true;
-        ++guard;
-#pragma unroll
-        for (int p = 1; p < n; ++p)
-#pragma unroll
-            for (int q = 0; q < p; ++q) {
-                double threshold = considerAsZero > precision * maxDiag ? considerAsZero : precision * maxDiag;
-                if (fabs(Wk[p + q * n]) > threshold || fabs(Wk[q + p * n]) > threshold) {
-                    finished = false;
-                    // real_2x2_jacobi_svd
-                    double m00 = Wk[p + p * n], m01 = Wk[p + q * n], m10 = Wk[q + p * n], m11 = Wk[q + q * n];
-                    JRot rot1;
-                    double t = m00 + m11;
-                    double d = m10 - m01;
-                    if (fabs(d) < DBL_MIN) {
-                        rot1.s = 0; rot1.c = 1;
-                    } else {
-                        double u = t / d;
-                        double tmp = sqrt(1 + u * u);
-                        rot1.s = 1 / tmp;
-                        rot1.c = u / tmp;
-                    }
-                    if (!(rot1.c == 1 && rot1.s == 0)) {
-                        double a0 = m00, b0 = m10, a1 = m01, b1 = m11;
-                        m00 = rot1.c * a0 + rot1.s * b0;
-                        m10 = -rot1.s * a0 + rot1.c * b0;
-                        m01 = rot1.c * a1 + rot1.s * b1;
-                        m11 = -rot1.s * a1 + rot1.c * b1;
-                    }
-                    JRot jr = make_jacobi(m00, m01, m11);
-                    JRot jl;
-                    {
-                        const double jtc = jr.c, jts = -jr.s;
-                        jl.c = rot1.c * jtc - rot1.s * jts;
-                        jl.s = rot1.c * jts + rot1.s * jtc;
-                    }
-                    // work.applyOnTheLeft(p, q, jl): rows p, q
-                    if (!(jl.c == 1 && jl.s == 0)) {
-#pragma unroll
-                        for (int i = 0; i < n; ++i) {
-                            double xi = Wk[p + i * n], yi = Wk[q + i * n];
-                            Wk[p + i * n] = jl.c * xi + jl.s * yi;
-                            Wk[q + i * n] = -jl.s * xi + jl.c * yi;
-                        }
-                    }
-                    // work.applyOnTheRight(p, q, jr) and V.applyOnTheRight(p, q, jr): rotation by jr^T
-                    const double tc = jr.c, ts = -jr.s;
-                    if (!(tc == 1 && ts == 0)) {
-#pragma unroll
-                        for (int i = 0; i < n; ++i) {
-                            double xi = Wk[i + p * n], yi = Wk[i + q * n];
-                            Wk[i + p * n] = tc * xi + ts * yi;
-                            Wk[i + q * n] = -ts * xi + tc * yi;
-                        }
-#pragma unroll
-                        for (int i = 0; i < n; ++i) {
-                            double xi = V[i + p * n], yi = V[i + q * n];
-                            V[i + p * n] = tc * xi + ts * yi;
-                            V[i + q * n] = -ts * xi + tc * yi;
-                        }
-                    }
-                    double aa = fabs(Wk[p + p * n]), bb = fabs(Wk[q + q * n]);
-                    double mx = aa > bb ? aa : bb;
-                    if (mx > maxDiag) maxDiag = mx;
-                }
-            }
-    }
-#pragma unroll
-    for (int i = 0; i < n; ++i) sv[i] = fabs(Wk[i + i * n]) * scale;
-#pragma unroll
-    for (int i = 0; i < n; ++i) {
-        int pos = i;
-        double mx = sv[i];
-#pragma unroll
-        for (int k = i + 1; k < n; ++k)
-            if (sv[k] > mx) { mx = sv[k]; pos = k; }
-        if (mx == 0) break;
-        if (pos != i) {
-            // swap sv[i] <-> sv[pos] and V columns, static indices only
-#pragma unroll
-            for (int k = i + 1; k < n; ++k)
-                if (k == pos) {
-                    double t = sv[i]; sv[i] = sv[k]; sv[k] = t;
-#pragma unroll
-                    for (int r = 0; r < n; ++r) { t = V[r + k * n]; V[r + k * n] = V[r + i * n]; V[r + i * n] = t; }
-                }
-        }
-    }
-    return true;
-}
-
-// LoopHandler::triangulation of one match (pixel2camera of both integer pixels, DLT rows, Eigen JacobiSVD);
-// returns success (s4/s3 < 1e-2) && Z > 0, the triangulate2View acceptance test (src/LoopHandler.cc:676)
-// SUBPIX (yv_stereo_subpix's refinement): the second pixel's column is y2 + dq / 256 (exact in double: |dq| < 2^12 and
-// y2 < 2^31 leave the sum inside 53 bits) in place of y2; nothing else changes.
-template <bool SUBPIX = false>
-__device__ bool triangulate_px(int x1, int y1, int x2, int y2, const double* Ta, const double* Tb,
-                               const double* K, double* Xo, int dq = 0) {
-    const double K0 = K[0], K2 = K[2], K4 = K[4], K5 = K[5];
-    double y2d = (double)y2;
-    if constexpr (SUBPIX) y2d = (double)y2 + (double)dq * (1.0 / 256.0);
-    const double pa[2] = {((double)x1 - K2) * 1.0 / K0, ((double)y1 - K5) * 1.0 / K4};
-    const double pb[2] = {((double)x2 - K2) * 1.0 / K0, (y2d - K5) * 1.0 / K4};
-    double A[16];
-#pragma unroll
-    for (int v = 0; v < 2; ++v) {
-        const double* T = v == 0 ? Ta : Tb;
-        const double* pp = v == 0 ? pa : pb;
-        double R[9];
-        quat_to_R(T, R);
-        double mm[12];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            mm[4 * r] = R[3 * r]; mm[4 * r + 1] = R[3 * r + 1]; mm[4 * r + 2] = R[3 * r + 2]; mm[4 * r + 3] = T[4 + r];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            A[(2 * v) + 4 * j] = pp[0] * mm[8 + j] - mm[j];
-            A[(2 * v + 1) + 4 * j] = pp[1] * mm[8 + j] - mm[4 + j];
-        }
-    }
-    double sv[4], V[16];
-    double X0 = NAN, X1 = NAN, X2 = NAN;
-    bool s = false;
-    if (eigen_jacobi_svd4(A, sv, V)) {
-        X0 = V[0 + 12] / V[3 + 12];
-        X1 = V[1 + 12] / V[3 + 12];
-        X2 = V[2 + 12] / V[3 + 12];
-        s = sv[3] / sv[2] < 1e-2;
-    }
-    Xo[0] = X0;
-    Xo[1] = X1;
-    Xo[2] = X2;
-    return s && X2 > 0;
-}
-
 template <bool SUBPIX>
 __global__ __launch_bounds__(256) void triangulate_kernel(const yv_match* __restrict__ m, int n, const double* __restrict__ poses /*[2][7]*/,
                                    const double* __restrict__ K, double* __restrict__ Xw, uint8_t* __restrict__ ok,
@@ -1437,182 +1229,6 @@ __global__ __launch_bounds__(NT) YAVO_LM_ATTR void pose_lm_kernel(const int32_t*
     pose_lm_body<NT>(offsets, counts, stride, Xall, uvall, Kall, priors, poses, outlier_all, inliers, n_prob);
 }
 
-// Track edges of the batched frontend: track t = {stereo pair sp, temporal pair tp} with
-// pairs[sp].query == pairs[tp].train (frame k's left image).  For temporal query i (frame k-1 keypoint)
-// kept by removeOutliers with best train keypoint j of frame k, and j's stereo match kept with right-image
-// keypoint r: X = triangulate(kp_k[j], kp_right[r]) with the left camera as world (pose identity) and the
-// right camera at T_right; accepted iff triangulation succeeds and Z > 0 (triangulate2View,
-// src/LoopHandler.cc:658-726).  uv = (kp_{k-1}[i].x, kp_{k-1}[i].y) (the reference's measurement,
-// src/LoopHandler.cc:786).  Edges keep temporal query order.  One workgroup per track.
-// KEEP (the match filter is on): a temporal match i counts only if keep[tp][i], its stereo match only if keep[sp][j].
-// SUBPIX (the stereo refinement is on): the stereo match triangulates from its refined right column (sub_dcol[sp][j],
-// zero unless its status is OK) and, with drop_edge, does not count when its status is EDGE.
-template <int NT, bool KEEP, bool SUBPIX>
-__global__ __launch_bounds__(NT) void track_build_kernel(
-    const int32_t* __restrict__ tracks, const int32_t* __restrict__ pairs, const yv_keypoint* __restrict__ keypoints,
-    const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj, const int32_t* __restrict__ match_lim,
-    int max_kp, const double* __restrict__ Kall, const double* __restrict__ T_right, double* __restrict__ edge_X,
-    double* __restrict__ edge_uv, int32_t* __restrict__ edge_query, int32_t* __restrict__ edge_count,
-    const uint8_t* __restrict__ keep, const int32_t* __restrict__ sub_dcol, const uint8_t* __restrict__ sub_status,
-    int drop_edge) {
-    __shared__ int s_tmp[40];
-    __shared__ double s_K[9], s_Ta[7], s_Tb[7];
-    const int t = blockIdx.x, tid = threadIdx.x;
-    const int sp = tracks[2 * t], tp = tracks[2 * t + 1];
-    const int qs = pairs[2 * sp], rs = pairs[2 * sp + 1];  // frame k left, frame k right
-    const int qt = pairs[2 * tp];                          // frame k-1 left
-    if (tid < 9) s_K[tid] = Kall[9 * t + tid];
-    if (tid < 7) {
-        s_Ta[tid] = tid == 3 ? 1.0 : 0.0;
-        s_Tb[tid] = T_right[tid];
-    }
-    __syncthreads();
-    const int nq = kp_count[qt];
-    const int lim_t = match_lim[tp], lim_s = match_lim[sp];
-    const int2* dj_t = match_dj + (int64_t)tp * max_kp;
-    const int2* dj_s = match_dj + (int64_t)sp * max_kp;
-    const yv_keypoint* kq = keypoints + (int64_t)qt * max_kp;
-    const yv_keypoint* kl = keypoints + (int64_t)qs * max_kp;
-    const yv_keypoint* kr = keypoints + (int64_t)rs * max_kp;
-    double* Xo = edge_X + 3 * (int64_t)t * max_kp;
-    double* uvo = edge_uv + 2 * (int64_t)t * max_kp;
-    int32_t* qo = edge_query + (int64_t)t * max_kp;
-    int ne = 0;
-    for (int base = 0; base < nq; base += NT) {
-        const int i = base + tid;
-        bool good = false;
-        double X[3];
-        if (i < nq) {
-            const int2 a = dj_t[i];
-            bool kt = true;
-            if constexpr (KEEP) kt = keep[(int64_t)tp * max_kp + i] != 0;
-            if (a.x < lim_t && a.y >= 0 && kt) {
-                const int2 b = dj_s[a.y];
-                bool ks = true;
-                if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + a.y] != 0;
-                int dq = 0;
-                if constexpr (SUBPIX) {
-                    dq = sub_dcol[(int64_t)sp * max_kp + a.y];
-                    if (drop_edge && sub_status[(int64_t)sp * max_kp + a.y] == kSubpixEdge) ks = false;
-                }
-                if (b.x < lim_s && b.y >= 0 && ks)
-                    good = triangulate_px<SUBPIX>(kl[a.y].x, kl[a.y].y, kr[b.y].x, kr[b.y].y, s_Ta, s_Tb, s_K, X, dq);
-            }
-        }
-        int tot = 0;
-        const int off = block_excl_scan_geom<NT>(good ? 1 : 0, s_tmp, &tot);
-        if (good) {
-            const int e = ne + off;
-            Xo[3 * e] = X[0];
-            Xo[3 * e + 1] = X[1];
-            Xo[3 * e + 2] = X[2];
-            uvo[2 * e] = (double)kq[i].x;
-            uvo[2 * e + 1] = (double)kq[i].y;
-            qo[e] = i;
-        }
-        ne += tot;
-    }
-    if (tid == 0) edge_count[t] = ne;
-}
-
-// LK tracking mode (the reference's trackLastFrame, src/LoopHandler.cc:298-454).  Map points of frame k-1: its
-// left keypoints whose stereo match (pair sp) survives removeOutliers and triangulates (left camera = world).
-// Compacted in keypoint order: X, the LK start point (x = column, y = row as cv::Point2f, :344) and the
-// keypoint index.  One workgroup per track.
-// KEEP / SUBPIX: as in track_build_kernel.
-template <int NT, bool KEEP, bool SUBPIX>
-__global__ __launch_bounds__(NT) void stereo_points_kernel(
-    const int32_t* __restrict__ stereo_pairs, const int32_t* __restrict__ pairs,
-    const yv_keypoint* __restrict__ keypoints, const int32_t* __restrict__ kp_count, const int2* __restrict__ match_dj,
-    const int32_t* __restrict__ match_lim, int max_kp, const double* __restrict__ Kall,
-    const double* __restrict__ T_right, double* __restrict__ pX, float* __restrict__ pts, int32_t* __restrict__ pq,
-    int32_t* __restrict__ pcount, const uint8_t* __restrict__ keep, const int32_t* __restrict__ sub_dcol,
-    const uint8_t* __restrict__ sub_status, int drop_edge) {
-    __shared__ int s_tmp[40];
-    __shared__ double s_K[9], s_Ta[7], s_Tb[7];
-    const int t = blockIdx.x, tid = threadIdx.x;
-    const int sp = stereo_pairs[t];
-    const int qs = pairs[2 * sp], rs = pairs[2 * sp + 1];
-    if (tid < 9) s_K[tid] = Kall[9 * t + tid];
-    if (tid < 7) {
-        s_Ta[tid] = tid == 3 ? 1.0 : 0.0;
-        s_Tb[tid] = T_right[tid];
-    }
-    __syncthreads();
-    const int nq = kp_count[qs];
-    const int lim = match_lim[sp];
-    const int2* dj = match_dj + (int64_t)sp * max_kp;
-    const yv_keypoint* kl = keypoints + (int64_t)qs * max_kp;
-    const yv_keypoint* kr = keypoints + (int64_t)rs * max_kp;
-    double* Xo = pX + 3 * (int64_t)t * max_kp;
-    float* po = pts + 2 * (int64_t)t * max_kp;
-    int32_t* qo = pq + (int64_t)t * max_kp;
-    int ne = 0;
-    for (int base = 0; base < nq; base += NT) {
-        const int j = base + tid;
-        bool good = false;
-        double X[3];
-        if (j < nq) {
-            const int2 a = dj[j];
-            bool ks = true;
-            if constexpr (KEEP) ks = keep[(int64_t)sp * max_kp + j] != 0;
-            int dq = 0;
-            if constexpr (SUBPIX) {
-                dq = sub_dcol[(int64_t)sp * max_kp + j];
-                if (drop_edge && sub_status[(int64_t)sp * max_kp + j] == kSubpixEdge) ks = false;
-            }
-            if (a.x < lim && a.y >= 0 && ks)
-                good = triangulate_px<SUBPIX>(kl[j].x, kl[j].y, kr[a.y].x, kr[a.y].y, s_Ta, s_Tb, s_K, X, dq);
-        }
-        int tot = 0;
-        const int off = block_excl_scan_geom<NT>(good ? 1 : 0, s_tmp, &tot);
-        if (good) {
-            const int e = ne + off;
-            Xo[3 * e] = X[0];
-            Xo[3 * e + 1] = X[1];
-            Xo[3 * e + 2] = X[2];
-            po[2 * e] = (float)kl[j].y;      // cv::Point2i(kp.y, kp.x) -> Point2f: x = column
-            po[2 * e + 1] = (float)kl[j].x;  // y = row
-            qo[e] = j;
-        }
-        ne += tot;
-    }
-    if (tid == 0) pcount[t] = ne;
-}
-
-// Pose edges from the LK result: points with status 1 become features at cv::Point2i(next.y, next.x), i.e. the
-// float coordinates truncated toward zero (src/LoopHandler.cc:395), measurement (kp.x, kp.y) = (row, col).
-__global__ __launch_bounds__(kNT) void lk_edges_kernel(const double* __restrict__ pX, const float* __restrict__ next,
-                                                       const uint8_t* __restrict__ status,
-                                                       const int32_t* __restrict__ pq,
-                                                       const int32_t* __restrict__ pcount, int max_kp,
-                                                       double* __restrict__ edge_X, double* __restrict__ edge_uv,
-                                                       int32_t* __restrict__ edge_query,
-                                                       int32_t* __restrict__ edge_count) {
-    __shared__ int s_tmp[40];
-    const int t = blockIdx.x, tid = threadIdx.x;
-    const int n = pcount[t];
-    const int64_t b = (int64_t)t * max_kp;
-    int ne = 0;
-    for (int base = 0; base < n; base += kNT) {
-        const int i = base + tid;
-        const bool good = i < n && status[b + i];
-        int tot = 0;
-        const int off = block_excl_scan_geom(good ? 1 : 0, s_tmp, &tot);
-        if (good) {
-            const int64_t e = b + ne + off;
-            edge_X[3 * e] = pX[3 * (b + i)];
-            edge_X[3 * e + 1] = pX[3 * (b + i) + 1];
-            edge_X[3 * e + 2] = pX[3 * (b + i) + 2];
-            edge_uv[2 * e] = (double)(int)next[2 * (b + i) + 1];  // kp.x = (int) row
-            edge_uv[2 * e + 1] = (double)(int)next[2 * (b + i)];  // kp.y = (int) column
-            edge_query[e] = pq[b + i];
-        }
-        ne += tot;
-    }
-    if (tid == 0) edge_count[t] = ne;
-}
-
 __global__ __launch_bounds__(kNT) void pose_gn_kernel(const int32_t* __restrict__ offsets, const double* __restrict__ Xall,
                                                       const double* __restrict__ uvall, const double* __restrict__ Kall,
                                                       double* __restrict__ poses, int32_t* __restrict__ iters_out) {
@@ -1768,70 +1384,6 @@ void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, con
     else
         geom::launch_lm(n_problems, s, offsets, static_cast<const int32_t*>(nullptr), 0, X, uv, K,
                         static_cast<const double*>(poses), poses, outlier, inliers);
-}
-
-void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
-                        const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
-                        const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s, const uint8_t* keep, const SubpixUse* sub) {
-    if (n_tracks <= 0) return;
-    const int32_t* sd = sub ? sub->dcol_q8 : nullptr;
-    const uint8_t* ss = sub ? sub->status : nullptr;
-    const int de = sub && sub->drop_edge ? 1 : 0;
-    // 1024 threads: about one query keypoint per thread (the FP64 triangulations are latency-bound; 256 / 512 were
-    // measured)
-    if (sub && keep)
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, true, true>), dim3(n_tracks), dim3(1024), 0, s, tracks,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
-                           edge_query, edge_count, keep, sd, ss, de);
-    else if (sub)
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, false, true>), dim3(n_tracks), dim3(1024), 0, s, tracks,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
-                           edge_query, edge_count, keep, sd, ss, de);
-    else if (keep)
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, true, false>), dim3(n_tracks), dim3(1024), 0, s, tracks,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
-                           edge_query, edge_count, keep, sd, ss, de);
-    else
-        hipLaunchKernelGGL((geom::track_build_kernel<1024, false, false>), dim3(n_tracks), dim3(1024), 0, s, tracks,
-                           pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, edge_X, edge_uv,
-                           edge_query, edge_count, keep, sd, ss, de);
-}
-
-void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
-                          const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
-                          const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep,
-                          const SubpixUse* sub) {
-    if (n_tracks <= 0) return;
-    const int32_t* sd = sub ? sub->dcol_q8 : nullptr;
-    const uint8_t* ss = sub ? sub->status : nullptr;
-    const int de = sub && sub->drop_edge ? 1 : 0;
-    // 1024 threads: about one keypoint per thread (FP64 triangulations, latency-bound)
-    if (sub && keep)
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true, true>), dim3(n_tracks), dim3(1024), 0, s,
-                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
-                           pq, pcount, keep, sd, ss, de);
-    else if (sub)
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false, true>), dim3(n_tracks), dim3(1024), 0, s,
-                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
-                           pq, pcount, keep, sd, ss, de);
-    else if (keep)
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, true, false>), dim3(n_tracks), dim3(1024), 0, s,
-                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
-                           pq, pcount, keep, sd, ss, de);
-    else
-        hipLaunchKernelGGL((geom::stereo_points_kernel<1024, false, false>), dim3(n_tracks), dim3(1024), 0, s,
-                           stereo_pairs, pairs, keypoints, kp_count, match_dj, match_lim, max_kp, K, T_right, pX, pts,
-                           pq, pcount, keep, sd, ss, de);
-}
-
-void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,
-                     const int32_t* pcount, int max_kp, double* edge_X, double* edge_uv, int32_t* edge_query,
-                     int32_t* edge_count, hipStream_t s) {
-    if (n_tracks <= 0) return;
-    hipLaunchKernelGGL(geom::lk_edges_kernel, dim3(n_tracks), dim3(geom::kNT), 0, s, pX, next, status, pq, pcount,
-                       max_kp, edge_X, edge_uv, edge_query, edge_count);
 }
 
 void launch_track_pose(int n_tracks, const int32_t* edge_count, int stride, const double* edge_X,

@@ -1,7 +1,7 @@
 // yavo_host.h -- what the host side of the C ABI shares between its translation units (yavo_api.hip, yavo_batch.hip,
-// yavo_geom_host.hip and the ABI parts of yavo_lk.hip, yavo_essential.hip, yavo_ba.hip): error handling, the owner of
-// what the HIP runtime hands out, the context and the batch, and the context's two host staging mechanisms.  Host code
-// only: nothing here is passed to a kernel.
+// yavo_batch_track.hip, yavo_geom_host.hip and the ABI parts of yavo_lk.hip, yavo_essential.hip, yavo_ba.hip): error
+// handling, the owner of what the HIP runtime hands out, the context and the batch, and the context's two host staging
+// mechanisms.  Host code only: nothing here is passed to a kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -189,6 +189,17 @@ struct yv_ctx {
 // an LM deferred into the next run (overlap modes 2-4) does not hold up the next build.
 constexpr int kEdgeBufs = 3;
 
+namespace yavo {
+
+// the map block a track's LM is followed by (yv_batch_track_map)
+struct MapArgs {
+    int64_t first_frame = 0;
+    int kf_every = 1, max_kf = 1;
+    void* block = nullptr;
+};
+
+}  // namespace yavo
+
 struct yv_batch {
     yv_ctx* ctx = nullptr;
     int max_images = 0, H = 0, W = 0, max_kp = 0, max_pairs = 0, n_pairs = 0;
@@ -263,14 +274,15 @@ struct yv_batch {
     int32_t* tracks = nullptr;      // [max_tracks][2] {stereo pair, temporal pair}
     double* track_K = nullptr;      // [max_tracks][9]
     double* T_right = nullptr;      // [7]
-    // edge / LM buffers, double-buffered ([2][...]): with the LM on the side stream, track i's LM reads
-    // buffer i % 2 while track i + 1 builds into the other one
-    double* edge_X = nullptr;       // [2][max_tracks][max_kp][3]
-    double* edge_uv = nullptr;      // [2][max_tracks][max_kp][2]
-    int32_t* edge_query = nullptr;  // [2][max_tracks][max_kp]
-    int32_t* edge_count = nullptr;  // [2][max_tracks]
-    uint8_t* edge_outlier = nullptr;
-    int32_t* track_inliers = nullptr;
+    // edge / LM buffers, kEdgeBufs of each ([kEdgeBufs][...], buffer k: edge_slice): track i builds into and its LM
+    // reads buffer i % kEdgeBufs; with the LM on the side stream the build of track i + kEdgeBufs waits for the LM of
+    // track i (ev_lm)
+    double* edge_X = nullptr;       // [kEdgeBufs][max_tracks][max_kp][3]
+    double* edge_uv = nullptr;      // [kEdgeBufs][max_tracks][max_kp][2]
+    int32_t* edge_query = nullptr;  // [kEdgeBufs][max_tracks][max_kp]
+    int32_t* edge_count = nullptr;  // [kEdgeBufs][max_tracks]
+    uint8_t* edge_outlier = nullptr;   // [kEdgeBufs][max_tracks][max_kp]
+    int32_t* track_inliers = nullptr;  // [kEdgeBufs][max_tracks]
     // LK tracking mode (yv_batch_set_track_lk): tracks are {stereo pair of frame k-1, image index of frame k}
     int lk_step = 0;                // > 0: LK mode, LK images are the run's images 0, lk_step, 2 lk_step, ...
     yv_lk* lk = nullptr;
@@ -304,9 +316,7 @@ struct yv_batch {
         double* poses = nullptr;
         hipEvent_t* ev = nullptr;   // stage timing events of the run the track belongs to
         bool has_map = false;
-        int64_t first_frame = 0;
-        int kf_every = 1, max_kf = 1;
-        void* block = nullptr;
+        yavo::MapArgs map;
     } deferred;
     hipEvent_t ev_defer = nullptr;
     hipStream_t side = nullptr;
@@ -445,5 +455,22 @@ int prepare_select(yv_batch* b, int H, int W);
 void launch_select_topk(yv_batch* b, int n_images, int keep, hipStream_t s);
 void launch_describe(yv_batch* b, int n_images, int max_workers, hipStream_t s);
 int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run);
+
+// ---- the track half of the batch (yavo_batch_track.hip), as yv_batch_run and the view need it ----
+constexpr int kEvPerRun = 9;  // stage timing events per recorded run (yv_batch::events)
+// the next writer of what an asynchronous edge build reads is ordered after it on stream s
+int join_build(yv_batch* b, hipStream_t s);
+// the deferred LM of the previous track, ordered after the work issued on s so far (the stage it waits for)
+int launch_deferred_after(yv_batch* b, hipStream_t s);
+// edge buffer k of kEdgeBufs (every pointer null while no tracks were set)
+struct EdgeSlice {
+    double* X;
+    double* uv;
+    int32_t* query;
+    int32_t* count;
+    uint8_t* outlier;
+    int32_t* inliers;
+};
+EdgeSlice edge_slice(const yv_batch* b, int k);
 
 }  // namespace yavo

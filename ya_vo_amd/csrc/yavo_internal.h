@@ -209,12 +209,6 @@ void launch_subpix_batch(const uint8_t* images, int n_images, int H, int W, int 
                          const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim,
                          const uint8_t* keep, int max_kp, int half_win, int search, const SubpixOut& out,
                          hipStream_t s);
-// what the track builders read of it: [pair][max_kp] arrays; drop_edge: a kSubpixEdge match counts as not kept
-struct SubpixUse {
-    const int32_t* dcol_q8;
-    const uint8_t* status;
-    bool drop_edge;
-};
 // removeOutliers on externally supplied Matches records (one list).
 void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
                            hipStream_t s);
@@ -256,20 +250,47 @@ void launch_lk_pyramid(const LkParams& P, int n_images, hipStream_t s);
 void launch_lk_derivs(const LkParams& P, int image, int level, int16_t* der, hipStream_t s);
 void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const float* pts, const int32_t* counts,
                      int pts_stride, int max_pts, float* next_pts, uint8_t* status, float* err, hipStream_t s);
-void launch_track_build(const int32_t* tracks, int n_tracks, const int32_t* pairs, const yv_keypoint* keypoints,
-                        const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim, int max_kp,
-                        const double* K, const double* T_right, double* edge_X, double* edge_uv, int32_t* edge_query,
-                        int32_t* edge_count, hipStream_t s, const uint8_t* keep = nullptr,
-                        const struct SubpixUse* sub = nullptr);
-// keep (optional, [pair][max_kp], the match filter's): a match counts only if its query's byte is set
-void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const int32_t* pairs,
-                          const yv_keypoint* keypoints, const int32_t* kp_count, const int2* match_dj,
-                          const int32_t* match_lim, int max_kp, const double* K, const double* T_right, double* pX,
-                          float* pts, int32_t* pq, int32_t* pcount, hipStream_t s, const uint8_t* keep = nullptr,
-                          const struct SubpixUse* sub = nullptr);
-void launch_lk_edges(int n_tracks, const double* pX, const float* next, const uint8_t* status, const int32_t* pq,
-                     const int32_t* pcount, int max_kp, double* edge_X, double* edge_uv, int32_t* edge_query,
-                     int32_t* edge_count, hipStream_t s);
+
+// ---- track composition (yavo_track.hip): a run's stereo and temporal matches into the pose LM's edges ----
+// What the track kernels read: the run's pair list, keypoints ([slot][max_kp]) and match records ([pair][max_kp]), the
+// tracks' K ([n_tracks][9]) and the right camera's pose T_right ([7]).  The rest is optional, [pair][max_kp]:
+// keep (the match filter's): a match counts only if its query's byte is set;
+// sub_dcol / sub_status (the stereo refinement's dcol_q8 and status, both or neither): a stereo match triangulates from
+// its refined right column and, with drop_edge, does not count when its status is kSubpixEdge.
+struct TrackSrc {
+    const int32_t* pairs;
+    const yv_keypoint* keypoints;
+    const int32_t* kp_count;
+    const int2* match_dj;
+    const int32_t* match_lim;
+    int max_kp;
+    const double* K;
+    const double* T_right;
+    const uint8_t* keep;
+    const int32_t* sub_dcol;
+    const uint8_t* sub_status;
+    bool drop_edge;
+};
+// What they write, track t at t * max_kp: the pose LM's edges ...
+struct EdgeOut {
+    double* X;       // [n_tracks][max_kp][3]
+    double* uv;      // [n_tracks][max_kp][2]
+    int32_t* query;  // [n_tracks][max_kp]
+    int32_t* count;  // [n_tracks]
+};
+// ... and LK mode's map points (pts: cv::Point2f, x = column)
+struct PointsOut {
+    double* X;
+    float* pts;
+    int32_t* query;
+    int32_t* count;
+};
+void launch_track_build(const int32_t* tracks, int n_tracks, const TrackSrc& src, const EdgeOut& out, hipStream_t s);
+void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const TrackSrc& src, const PointsOut& out,
+                          hipStream_t s);
+// edges of the points `pts` that LK tracked to `next` with `status` set (both [n_tracks][max_kp])
+void launch_lk_edges(int n_tracks, const PointsOut& pts, const float* next, const uint8_t* status, int max_kp,
+                     const EdgeOut& out, hipStream_t s);
 
 // cv::findEssentialMat (RANSAC) + cv::recoverPose (yavo_essential.hip).  Workspace of a yv_essential.
 // RANSAC iterations evaluated per round: 64, or 1024 (>= findEssentialMat's 1000) for workspaces of at most kEssWidePairs
