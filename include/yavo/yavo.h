@@ -310,9 +310,18 @@ int yv_batch_track(yv_batch* b, const double* d_priors, double* d_poses, void* s
  * track views are then complete only after yv_batch_track_sync (or a device-wide synchronization).  on = 2 / 3 / 4 defer each
  * LM further: it is launched by the next yv_batch_run once that run's detect (2) / describe (3) / top-K (4) stage is issued
  * (so it runs beside the later, less occupancy-sensitive stages), or by yv_batch_track_sync /
- * yv_batch_map_wait / the next yv_batch_track, whichever comes first. */
+ * yv_batch_map_wait / the next yv_batch_track, whichever comes first.
+ * With the match tracker, tracks set and the asynchronous edge build, a run's two lists of Matches records
+ * (yv_batch_view matches / filtered) are also written on a stream of the batch, beside the next run's detect: nothing
+ * in the step reads them.  They are then complete after yv_batch_track_sync, or on a stream that called
+ * yv_batch_records_wait after the run, and no longer after a synchronization of the run's stream alone.  The counts,
+ * match_dj, match_lim and every other view are written on the run's stream as before.  (Every-stage timing,
+ * yv_batch_enable_timing(b, 1), keeps the lists on the run's stream.) */
 int yv_batch_set_track_overlap(yv_batch* b, int on);
 int yv_batch_track_sync(yv_batch* b);
+/* `stream` waits for the last run's lists of Matches records where they are written beside the next run (overlap
+ * mode, above); otherwise a no-op: the lists are then ordered on the run's stream. */
+int yv_batch_records_wait(yv_batch* b, void* stream);
 /* LK tracking mode, the reference's trackLastFrame (src/LoopHandler.cc:298-454): with image_step > 0 a track
  * is {stereo pair of frame k-1, image index of frame k}.  Frame k-1's map points are its left keypoints whose
  * stereo match survives removeOutliers and triangulates; they are tracked into frame k by

@@ -127,6 +127,7 @@ SIGNATURES = {
     "yv_batch_track": (_I, [_P, _P, _P, _P]),
     "yv_batch_set_track_overlap": (_I, [_P, _I]),
     "yv_batch_track_sync": (_I, [_P]),
+    "yv_batch_records_wait": (_I, [_P, _P]),
     "yv_batch_set_track_lk": (_I, [_P, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double]),
 }
 
@@ -740,6 +741,11 @@ class Batch:
 
     def track_sync(self) -> None:
         _check(self.lib.yv_batch_track_sync(self.handle), "yv_batch_track_sync")
+
+    def records_wait(self, stream: int) -> None:
+        """`stream` waits for the last run's match / filtered lists where the overlap mode writes them beside the
+        next run (yv_batch_records_wait)."""
+        _check(self.lib.yv_batch_records_wait(self.handle, ctypes.c_void_p(stream)), "yv_batch_records_wait")
 
     def enable_timing(self, on=True) -> None:
         """on: False/0 off, True/1 every stage, 2 the detect kernel only (yavo.h)."""

@@ -210,6 +210,21 @@ int brief_workers(yv_ctx* ctx, int W) {
     return ctx->brief_cap > 0 ? std::min(w, ctx->brief_cap) : w;
 }
 
+int records_workgroups(yv_ctx* ctx) { return ctx_cus(ctx) * 8; }
+
+hipStream_t make_queue_stream(yv_ctx* ctx) {
+    const int cus = ctx_cus(ctx);
+    std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
+    for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
+    hipStream_t s = nullptr;
+    if (hipExtStreamCreateWithCUMask(&s, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
+        s = nullptr;
+        (void)hipGetLastError();
+        if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) s = nullptr;
+    }
+    return s;
+}
+
 }  // namespace yavo
 
 namespace {
@@ -367,14 +382,7 @@ void* yv_side_stream(yv_ctx* ctx) {
     if (!ctx) return nullptr;
     if (ctx->side) return reinterpret_cast<void*>(ctx->side);
     if (set_device(ctx) != YV_OK) return nullptr;
-    const int cus = ctx_cus(ctx);
-    std::vector<uint32_t> mask((size_t)(cus + 31) / 32, 0u);
-    for (int c = 0; c < cus; ++c) mask[(size_t)c / 32] |= 1u << (c % 32);
-    if (hipExtStreamCreateWithCUMask(&ctx->side, (uint32_t)mask.size(), mask.data()) != hipSuccess) {
-        ctx->side = nullptr;
-        (void)hipGetLastError();
-        if (hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking) != hipSuccess) ctx->side = nullptr;
-    }
+    ctx->side = make_queue_stream(ctx);
     if (ctx->side) ctx->mem.adopt(ctx->side);
     return reinterpret_cast<void*>(ctx->side);
 }

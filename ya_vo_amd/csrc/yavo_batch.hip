@@ -32,8 +32,16 @@ int record_stage(yv_batch* b, hipStream_t s, int run, int stage) {
 
 yavo::MatchLists match_lists(const yv_batch* b) { return {b->desc, b->keypoints, b->kp_count, b->max_kp}; }
 
-yavo::MatchRecords match_records(const yv_batch* b) {
-    return {b->matches, b->match_count, b->filtered, b->filt_count, b->match_dj, b->match_lim};
+// (deferred: the finalize leaves the two lists to launch_match_records)
+yavo::MatchRecords match_records(const yv_batch* b, bool deferred) {
+    return {b->matches,  b->match_count, b->filtered, b->filt_count,
+            b->match_dj, b->match_lim,   deferred ? b->match_pos : nullptr};
+}
+
+// the deferred records' filtered positions, on first use
+int ensure_match_pos(yv_batch* b) {
+    if (b->match_pos) return YV_OK;
+    return b->mem.alloc(&b->match_pos, (size_t)std::max(b->max_pairs, 1) * (size_t)b->max_kp);
 }
 
 static_assert(YV_SUBPIX_NONE == yavo::kSubpixNone && YV_SUBPIX_OK == yavo::kSubpixOk &&
@@ -74,6 +82,7 @@ void batch_free(yv_batch* b) {
     if (!b) return;
     if (b->bstream) (void)hipStreamSynchronize(b->bstream);
     if (b->side) (void)hipStreamSynchronize(b->side);
+    if (b->rstream) (void)hipStreamSynchronize(b->rstream);  // (the owner destroys streams before it frees memory)
     if (b->lk) yv_lk_destroy(b->lk);
     delete b;
 }
@@ -258,8 +267,19 @@ int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run) {
     }
     const int rc = record_stage(b, s, run, 4);
     const yavo::FinalizeRobust rb{b->match_key2, b->rev_key, st.flags, st.num, st.den, b->nn2, b->rev, b->keep};
-    yavo::launch_match_finalize(b->match_key, lists, b->pairs, st.n_pairs, st.thr, match_records(b),
-                                st.top2 ? &rb : nullptr, s, st.kp_count_copy, st.n_slots);
+    const yavo::MatchRecords out = match_records(b, st.defer_records);
+    yavo::launch_match_finalize(b->match_key, lists, b->pairs, st.n_pairs, st.thr, out, st.top2 ? &rb : nullptr, s,
+                                st.kp_count_copy, st.n_slots);
+    if (st.defer_records) {
+        // the lists beside whatever follows on s; they read the finalize's copy of the counts (the next run's top-K
+        // rewrites kp_count) and the keypoints, whose next writer joins (join_records)
+        YV_HIP(hipEventRecord(b->ev_keys, s));
+        YV_HIP(hipStreamWaitEvent(b->rstream, b->ev_keys, 0));
+        yavo::launch_match_records({lists.desc, lists.keypoints, st.kp_count_copy, lists.max_kp}, b->pairs, st.n_pairs,
+                                   out, records_workgroups(b->ctx), b->rstream);
+        YV_HIP(hipEventRecord(b->ev_records, b->rstream));
+        b->records_pending = true;
+    }
     return rc;
 }
 
@@ -352,6 +372,7 @@ int yv_batch_set_pairs(yv_batch* b, const int32_t* pairs, int n_pairs) {
     if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
     if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // an edge build in flight reads pairs
     b->build_pending = false;
+    if (drain_records(b) != YV_OK) return YV_ERR_HIP;  // and so do deferred match records
     if (n_pairs > 0) {
         YV_HIP(hipMemcpyAsync(b->pairs, pairs, sizeof(int32_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice,
                               b->ctx->stream));
@@ -517,7 +538,9 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     if (sel != YV_OK) return sel;
     const bool steer = steer_on(ctx);
     if (steer && ensure_steer(b) != YV_OK) return YV_ERR_HIP;
-    if (b->pending_carry >= 0 && join_build(b, s) != YV_OK) return YV_ERR_HIP;
+    const bool defer_records = b->rstream && b->n_tracks > 0 && b->timing != 1;  // (with copy_counts below)
+    if (defer_records && ensure_match_pos(b) != YV_OK) return YV_ERR_HIP;
+    if (b->pending_carry >= 0 && (join_build(b, s) != YV_OK || join_records(b, s) != YV_OK)) return YV_ERR_HIP;
     if (b->pending_carry >= 0) {
         const size_t c = (size_t)b->pending_carry, dst = (size_t)b->max_images, nk = (size_t)K;
         YV_HIP(hipMemcpyAsync(b->keypoints + dst * nk, b->keypoints + c * nk, nk * sizeof(yv_keypoint),
@@ -546,6 +569,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
     // (its keypoint counts are a copy, kp_count_build, so top-K need not wait)
     rc |= join_build(b, s);
+    rc |= join_records(b, s);  // and the previous run's deferred match records read keypoints
     launch_describe(b, n_images, brief_workers(ctx, W), s);
     rc |= record_stage(b, s, run, 3);
     if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
@@ -553,6 +577,10 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     // the asynchronous edge build reads a copy of the keypoint counts (the next run's top-K rewrites them):
     // the finalize kernel writes it, where a separate device copy waited ~50 us for a CU at the end of the step
     const bool copy_counts = b->n_pairs > 0 && b->overlap && b->build_async && b->lk_step == 0;
+    // In that pipelined mode with tracks, nothing later in the step reads the two lists of Matches records (the build
+    // and the sub-pixel stage read match_dj / match_lim / keep): they are written on the records stream beside the next
+    // run's detect.  The every-stage timing keeps the fused finalize, so its finalize stage stays the whole finalize.
+    const bool defer = copy_counts && defer_records;
     if (b->n_pairs > 0) {
         // with the match filter: top-2 forward, the swapped pairs for the cross-check, then the filtering finalize
         MatchStage st;
@@ -567,6 +595,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
         st.den = b->ratio_den;
         st.kp_count_copy = copy_counts ? b->kp_count_build : nullptr;
         st.n_slots = b->nslots;
+        st.defer_records = defer;
         rc |= match_stage(b, st, s, run);
         // the stereo refinement of the marked pairs, on the finalize's match_dj / match_lim / keep and the raw images
         if (b->subpix_on)

@@ -21,6 +21,20 @@ int join_build(yv_batch* b, hipStream_t s) {
     return YV_OK;
 }
 
+// (what the deferred match records read: the counts' copy, keypoints, match_dj, match_pos, pairs)
+int join_records(yv_batch* b, hipStream_t s) {
+    if (!b->records_pending) return YV_OK;
+    YV_HIP(hipStreamWaitEvent(s, b->ev_records, 0));
+    b->records_pending = false;
+    return YV_OK;
+}
+
+int drain_records(yv_batch* b) {
+    if (b->rstream) YV_HIP(hipStreamSynchronize(b->rstream));
+    b->records_pending = false;
+    return YV_OK;
+}
+
 EdgeSlice edge_slice(const yv_batch* b, int k) {
     if (!b->edge_X) return {};
     const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
@@ -212,6 +226,7 @@ int yv_batch_set_tracks(yv_batch* b, const int32_t* tracks, int n_tracks, const 
     hipStream_t s = b->ctx->stream;
     if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // a build in flight reads tracks / K
     b->build_pending = false;
+    if (drain_records(b) != YV_OK) return YV_ERR_HIP;  // (as every call that drains the build)
     if (b->side) YV_HIP(hipStreamSynchronize(b->side));  // an LM in flight reads tracks / K
     if (n_tracks > b->max_tracks) {
         YV_HIP(hipStreamSynchronize(s));
@@ -314,9 +329,17 @@ int yv_batch_set_track_overlap(yv_batch* b, int on) {
         b->mem.adopt(b->bstream);
         YV_HIP(b->mem.event(&b->ev_fin));
         YV_HIP(b->mem.event(&b->ev_built));
+        // the records stream on a hardware queue of its own: a fifth plain stream would share one of the four queues,
+        // and on the context stream's the records would run in order after all (see yv_side_stream)
+        b->rstream = make_queue_stream(b->ctx);
+        if (!b->rstream) return YV_ERR_HIP;
+        b->mem.adopt(b->rstream);
+        YV_HIP(b->mem.event(&b->ev_keys));
+        YV_HIP(b->mem.event(&b->ev_records));
     }
     if (!on && b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
     if (!on) b->build_pending = false;
+    if (!on && drain_records(b) != YV_OK) return YV_ERR_HIP;
     {
         const char* e = std::getenv("YAVO_BUILD_ASYNC");
         b->build_async = on != 0 && !(e && e[0] == '0');
@@ -333,6 +356,14 @@ int yv_batch_track_sync(yv_batch* b) {
     if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
     if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));
     if (b->side) YV_HIP(hipStreamSynchronize(b->side));
+    return drain_records(b);  // the last run's match and filtered lists are complete
+}
+
+int yv_batch_records_wait(yv_batch* b, void* stream) {
+    if (!b || !stream) return YV_ERR_INVALID;
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    // (the flag stays: the next writer of the keypoints still joins on its own stream)
+    if (b->records_pending) YV_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), b->ev_records, 0));
     return YV_OK;
 }
 
@@ -344,6 +375,7 @@ int yv_batch_set_track_lk(yv_batch* b, int image_step, int win, int max_level, i
     if (b->side) YV_HIP(hipStreamSynchronize(b->side));
     if (b->bstream) YV_HIP(hipStreamSynchronize(b->bstream));  // an edge build in flight (as its siblings drain)
     b->build_pending = false;
+    if (drain_records(b) != YV_OK) return YV_ERR_HIP;
     YV_HIP(hipStreamSynchronize(b->ctx->stream));
     if (b->lk) {
         yv_lk_destroy(b->lk);

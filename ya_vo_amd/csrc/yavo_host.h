@@ -326,6 +326,13 @@ struct yv_batch {
     hipStream_t bstream = nullptr;
     bool build_async = false, build_pending = false;
     hipEvent_t ev_fin = nullptr, ev_built = nullptr;
+    // match records beside the next run (pipelined mode, see yv_batch_run): the finalize on the run's stream writes
+    // the keys' results and match_pos only (ev_keys), match_records_kernel writes the two lists on `rstream`
+    // (ev_records); the next writer of the keypoints it reads waits for it (join_records)
+    hipStream_t rstream = nullptr;
+    hipEvent_t ev_keys = nullptr, ev_records = nullptr;
+    bool records_pending = false;
+    int32_t* match_pos = nullptr;   // [max_pairs][max_kp] position in the filtered list, -1: dropped (on first use)
     hipEvent_t ev_edges[kEdgeBufs] = {}, ev_lm[kEdgeBufs] = {};
     bool lm_pending[kEdgeBufs] = {};
     hipEvent_t ev_map = nullptr;    // after the last yv_batch_track_map's block (yv_batch_map_wait)
@@ -354,6 +361,11 @@ inline bool steer_on(const yv_ctx* ctx) { return ctx->steer_bins > 0; }
 // ---- the context (yavo_api.hip) ----
 // brief_kernel's worker limit for images W wide
 int brief_workers(yv_ctx* ctx, int W);
+// match_records_kernel's one-wave workgroups: two per SIMD
+int records_workgroups(yv_ctx* ctx);
+// A stream on a hardware queue of its own (see yv_side_stream): a CU mask with every CU enabled, or a plain
+// non-blocking stream where the runtime refuses the mask.  nullptr on failure; the caller owns the stream.
+hipStream_t make_queue_stream(yv_ctx* ctx);
 
 // Pinned staging of the host-pointer entry points (yv_ctx::h_stage): uploads are copied into the staging buffer and
 // DMA'd from it, downloads land in it and reach the caller's buffers in stage_sync.
@@ -441,6 +453,8 @@ struct MatchStage {
     int flags = 0, num = 0, den = 1;       // top2 only: the filter's tests
     int32_t* kp_count_copy = nullptr;      // optional: the finalize copies kp_count[0, n_slots) there
     int n_slots = 0;
+    bool defer_records = false;            // the record lists on b->rstream after the finalize (kp_count_copy is set,
+                                           // b->match_pos and b->rstream exist)
 };
 
 void batch_free(yv_batch* b);  // no drain of the context's stream: yv_batch_destroy's part
@@ -460,6 +474,10 @@ int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run);
 constexpr int kEvPerRun = 9;  // stage timing events per recorded run (yv_batch::events)
 // the next writer of what an asynchronous edge build reads is ordered after it on stream s
 int join_build(yv_batch* b, hipStream_t s);
+// the same for the deferred match records, which read the keypoints
+int join_records(yv_batch* b, hipStream_t s);
+// drains the records stream (before the host rewrites or frees what match_records_kernel reads or writes)
+int drain_records(yv_batch* b);
 // the deferred LM of the previous track, ordered after the work issued on s so far (the stage it waits for)
 int launch_deferred_after(yv_batch* b, hipStream_t s);
 // edge buffer k of kEdgeBufs (every pointer null while no tracks were set)

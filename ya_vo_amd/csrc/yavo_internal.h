@@ -102,7 +102,9 @@ struct MatchLists {
     int max_kp;
 };
 // The finalize's outputs per pair: all records and the kept ones ([pair][max_kp]) with their counts, every query's
-// {distance, train index} and the removeOutliers limit.
+// {distance, train index} and the removeOutliers limit.  match_pos != nullptr defers the two record lists: the finalize
+// then writes every query's position in the filtered list there ([pair][max_kp], -1: dropped) and leaves the lists to
+// launch_match_records.
 struct MatchRecords {
     yv_match* matches;
     int32_t* match_count;
@@ -110,6 +112,7 @@ struct MatchRecords {
     int32_t* filt_count;
     int2* match_dj;
     int32_t* match_lim;
+    int32_t* match_pos;
 };
 // Brute-force Hamming NN: match_key[pair][q] = min over t of (dist << 16 | t).  max_train bounds every train
 // list's length (<= 2048: the FP4 matcher, otherwise the int8 +-1 form).  match_key2 != nullptr: also every query's
@@ -137,6 +140,11 @@ struct FinalizeRobust {
 void launch_match_finalize(uint32_t* match_key, const MatchLists& lists, const int32_t* pairs, int n_pairs, int thr,
                            const MatchRecords& out, const FinalizeRobust* rb, hipStream_t s,
                            int32_t* kp_count_copy = nullptr, int n_slots = 0);
+// The record lists of a finalize that deferred them (out.match_pos set), byte for byte what the fused finalize writes:
+// from out.match_dj / out.match_pos, the pairs and the keypoints; lists.kp_count may be a copy of that run's counts.
+// At most max_workgroups one-wave workgroups walk the lists.
+void launch_match_records(const MatchLists& lists, const int32_t* pairs, int n_pairs, const MatchRecords& out,
+                          int max_workgroups, hipStream_t s);
 // The gated matcher (yv_match_gated / yv_batch_set_match_gates, yavo_match_gate.hip).  Per slot, the keypoints
 // bucketed by cell = (band of kGateBandRows rows, column >> col_shift): sorted[slot][max_kp] = {row | column << 16,
 // keypoint index} cell by cell, band_start[slot][n_bands + 1] = first entry of every band.  n_bands * kGateBandRows
