@@ -1,8 +1,8 @@
 """The front end over the whole (H, W, max_kp, image count) envelope that yv_batch_create accepts, against the oracle.
 
 The rest of the GPU suite runs detect -> top-K -> BRIEF -> match at KITTI size and below with max_kp = 2000.  The cases
-here are the smallest inputs that flip each size switch of ya_vo_amd/csrc/yavo_kernels.hip and of yv_batch_create /
-yv_batch_run (yavo_batch.hip):
+here are the smallest inputs that flip each size switch of the front-end kernels (ya_vo_amd/csrc/yavo_detect.hip,
+yavo_topk.hip, yavo_brief.hip, yavo_match.hip) and of yv_batch_create / yv_batch_run (yavo_batch.hip):
 
   * boundary_compact's (band, bank class) counters: 32 bands x 32 classes = 1024 counters (two trips of top-K's
     512-thread scan), one class above 32 bands (H > 1024), K > 2048 (two chunks of 4 x 512 points), 256 bands (every

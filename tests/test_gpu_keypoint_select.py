@@ -3,7 +3,7 @@ reference: non-maximum suppression among the FAST corners and per-cell quotas, b
 (~ord(response)) << 32 | row * W + col the cut itself ranks by (a smaller key is better).
 
 The reference below is the specification.  It builds the keys from (response, index) exactly as key_resp
-(ya_vo_amd/csrc/yavo_kernels.hip) inverts them, suppresses through a dense minimum-key map and the minimum over the
+(ya_vo_amd/csrc/yavo_internal.h) inverts them, suppresses through a dense minimum-key map and the minimum over the
 (2r + 1)^2 shifts of it (taken as 2r + 1 row shifts, then 2r + 1 column shifts: the same minimum), applies the quota by a
 lexsort on (cell, key) and the cut by a sort on the key.  With every parameter off it equals oracle.fast bit for bit
 (test_reference_off_equals_the_oracle, no GPU), which ties it to the oracle; every GPU comparison is exact.
@@ -46,7 +46,7 @@ def make_keys(idx, resp):
 
 
 def key_resp(keys):
-    """key_resp of yavo_kernels.hip: the response's bits back from a key"""
+    """key_resp of yavo_internal.h: the response's bits back from a key"""
     ordv = ~(keys >> np.uint64(32)).astype(np.uint32)
     u = np.where(ordv & np.uint32(0x80000000), ordv & np.uint32(0x7FFFFFFF), ~ordv).astype(np.uint32)
     return u.view(np.float32)

@@ -51,7 +51,7 @@ def test_ring_stl_containers_build_the_same_ring(oracle):
 
 
 def test_ring_table_in_kernel_matches_oracle(oracle):
-    src = open(os.path.join(ROOT, "ya_vo_amd", "csrc", "yavo_kernels.hip")).read()
+    src = open(os.path.join(ROOT, "ya_vo_amd", "csrc", "yavo_detect.hip")).read()
     dr = [int(v) for v in re.search(r"#define YV_RING_DR \{([^}]*)\}", src).group(1).split(",")]
     dc = [int(v) for v in re.search(r"#define YV_RING_DC \{([^}]*)\}", src).group(1).split(",")]
     assert list(zip(dr, dc)) == [tuple(map(int, p)) for p in oracle.ring(0, 0)]

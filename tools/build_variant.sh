@@ -7,7 +7,8 @@ TAG=$1; SRC=$2; DEFS=$3
 make -j16 >/dev/null
 mkdir -p ../build/var_$TAG
 EXTRA=""
-[ "$SRC" = "yavo_kernels" ] && EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1"
+# the Makefile's MFMA_OBJS: the two sources whose kernels use the matrix cores
+case "$SRC" in yavo_detect|yavo_match) EXTRA="-mllvm -amdgpu-mfma-vgpr-form=1" ;; esac
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-gpu-flush-denormals-to-zero \
     -fhip-fp32-correctly-rounded-divide-sqrt -Wall -Wno-unused-function $EXTRA $DEFS -c -o ../build/var_$TAG/$SRC.o $SRC.hip
 OBJS=$(ls ../build/*.o | grep -v "/$SRC.o$")

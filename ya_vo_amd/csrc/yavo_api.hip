@@ -1,6 +1,6 @@
 // yavo_api.hip -- the context's part of the C ABI of libyavo.so (include/yavo/yavo.h): create / destroy / setters,
 // streams, upload / download / alloc, the two host staging mechanisms (yavo_host.h), the single-image workspace and the
-// host-pointer drop-in entry points.  Host code only; kernels live in yavo_kernels.hip.  No CPU fallback exists: every
+// host-pointer drop-in entry points.  Host code only; kernels live in the stage files.  No CPU fallback exists: every
 // compute path runs the gfx950 kernels.
 #include "yavo_host.h"
 

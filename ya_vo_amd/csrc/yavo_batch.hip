@@ -1,7 +1,8 @@
 // yavo_batch.hip -- the batched device pipeline of the C ABI (include/yavo/yavo.h): yv_batch_* up to the run and the
 // view, the buffers, the match stage and the opt-in stages behind it, which the host-pointer front end (yavo_api.hip)
 // runs on its single-image workspace as well.  The tracks (yv_batch_set_tracks, yv_batch_track and what follows a run's
-// matches) are in yavo_batch_track.hip.  Host code only; kernels live in yavo_kernels.hip and its siblings.
+// matches) are in yavo_batch_track.hip.  Host code only; kernels live in the stage files (yavo_detect.hip .. yavo_match_finalize.hip
+// and the opt-in stages').
 #include "yavo_host.h"
 
 using namespace yavo;

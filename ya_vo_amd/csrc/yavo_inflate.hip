@@ -29,6 +29,7 @@
 #include <stdint.h>
 
 #include "yavo_internal.h"
+#include "yavo_wave.h"
 
 namespace yavo {
 namespace png {
@@ -83,15 +84,8 @@ __device__ __forceinline__ uint32_t sw(uint32_t i) { return i ^ ((i >> 5) & 31u)
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ uint32_t lane_of(uint32_t v, int l) { return __builtin_amdgcn_readlane(v, l); }
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return v;
-}
+// yavo_wave.h's DPP scan; every sum here (output and match counts, carries) is far below 2^31
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) { return (uint32_t)yavo::wave_incl_scan((int)v); }
 
 // ---- CRC-32 (ISO-HDLC: reflected polynomial 0xEDB88320, init and final XOR ~0; the PNG chunk CRC) ----
 constexpr uint32_t kCrcPoly = 0xEDB88320u;

@@ -19,8 +19,8 @@ __host__ __device__ inline double cube_cr(double t) {
     return q + (e2 + e1 * t);
 }
 
-constexpr int kMaxKp = 4096;
-constexpr int kMaxWidth = 2048;  // image width limit (BRIEF keeps 49 rows of the blurred image in LDS)       // per-image keypoint capacity supported by the top-K / scan kernels
+constexpr int kMaxKp = 4096;     // per-image keypoint capacity supported by the top-K / scan kernels
+constexpr int kMaxWidth = 2048;  // image width limit (BRIEF keeps 49 rows of the blurred image in LDS)
 // BRIEF's row bands: 32 image rows per workgroup.  top-K buckets each image's kept keypoints by band
 // (kp_band[image][max_kp] int4 {row, col, id, slot}, band b at [band_off[image][b], band_off[image][b + 1])), so a
 // BRIEF workgroup reads its band's keypoints only; H <= kBandRows * kMaxBands.
@@ -58,6 +58,7 @@ struct Desc {                      // 256-bit BRIEF descriptor, test j -> bit j 
     uint32_t w[8];
 };
 
+// ---- detect (yavo_detect.hip) ----
 // FAST-12 candidate test + Harris response, appends (response, index) keys per image.  eig: the cv::eigen
 // flavour (0 = JacobiImpl_, 1 = HAVE_EIGEN's SelfAdjointEigenSolver).
 void launch_fast_harris(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch,
@@ -72,6 +73,38 @@ void launch_detect_blur(const uint8_t* imgs, int n_images, int H, int W, int str
 // 9-tap separable fixed-point Gaussian, BORDER_REFLECT_101; output [image][H][blur_pitch(W)].
 void launch_blur9(const uint8_t* imgs, int n_images, int H, int W, int stride, int64_t pitch,
                   const uint16_t* k9_host, uint8_t* blur, hipStream_t s);
+// The key detect writes, select filters and top-K reads.  Order-preserving: ascending key == (response descending,
+// row-major index ascending).
+__device__ __forceinline__ uint64_t make_key(float resp, uint32_t idx) {
+    if (resp == 0.0f) resp = 0.0f;  // -0 and +0 compare equal in the reference's sort
+    uint32_t u = __float_as_uint(resp);
+    uint32_t ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((uint64_t)(~ord) << 32) | (uint64_t)idx;
+}
+__device__ __forceinline__ float key_resp(uint64_t key) {
+    uint32_t ord = ~(uint32_t)(key >> 32);
+    uint32_t u = (ord & 0x80000000u) ? (ord & 0x7fffffffu) : ~ord;
+    return __uint_as_float(u);
+}
+
+// ---- keypoint selection (yavo_select.hip) ----
+// Keypoint selection (yv_set_keypoint_select, yavo_select.hip): the filter between the detect kernel and launch_topk.
+// Suppression buckets the corners by tiles of kSelTileRows x kSelTileCols pixels, the quota by the caller's cells; both
+// grids have at most kSelMaxCells cells (the tiles of every accepted H x W do, the cells are the caller's to check).
+constexpr int kSelMaxCells = 8192;
+constexpr int kSelTileRows = 32, kSelTileCols = 64;
+constexpr int kSelMaxRadius = 8;
+constexpr int kSelMaxPerCell = 4096;
+constexpr int kSelMinCell = 8, kSelMaxCell = 8192;
+// Filters cand_keys[img][0 .. cand_count[img]) in place (nms_radius > 0: suppression; per_cell > 0: the quota) and does
+// launch_topk's bookkeeping for the detect kernel's list (cand_seen = corners before the filter, cand_count = 0).
+// scratch: n_images lists of cap keys; starts: [n_images][kSelMaxCells + 1]; counts: [2][n_images].  Returns the array
+// (inside counts) holding the filtered lists' lengths: launch_topk's cand_count, which resets it.
+uint32_t* launch_select(uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, uint32_t* cand_seen, int n_images,
+                        int H, int W, int nms_radius, int cell_rows, int cell_cols, int per_cell, uint64_t* scratch,
+                        int32_t* starts, uint32_t* counts, hipStream_t s);
+
+// ---- top-K (yavo_topk.hip) ----
 // Per-image top-K (response desc, index asc) + checkBoundry compaction.
 // cand_count is copied to cand_seen and reset to 0 after it is read (ready for the next detection).
 // brief_heads: the kBriefHeads queue heads of the launch_brief that follows on s, zeroed here (no launch of their own).
@@ -83,6 +116,8 @@ void launch_topk(const uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, u
 void launch_kp_boundary(const int32_t* det_rc, const int32_t* det_count, int n_images, int H, int W,
                         int max_kp, int32_t* kp_src, int32_t* kp_count, int32_t* kp_band, int32_t* band_off,
                         int32_t* brief_heads, hipStream_t s);
+
+// ---- BRIEF (yavo_brief.hip, yavo_steer.hip) ----
 // BRIEF: writes KeyPoint records + packed descriptors.  loff: a 2 KB device scratch of the caller holding the tests'
 // LDS offsets for this W, formed on stream s first when new_loff (the offsets table or W changed since it was formed).
 // heads: the band queue's kBriefHeads heads, zero on entry (launch_topk / launch_kp_boundary on s); the grid is
@@ -94,6 +129,30 @@ void launch_brief(const uint8_t* blur, int n_images, int H, int W, const int8_t*
 // Pack KeyPoint records -> descriptors (host-supplied keypoints).
 void launch_pack_desc(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp,
                       Desc* desc, hipStream_t s);
+// Rotation-steered BRIEF (yv_set_brief_steering, yavo_steer.hip): launch_brief's replacement while steering is on.
+// Every sample is the blurred image clamped to [0, H - 1] x [0, W - 1].  The kernel keeps a keypoint's patch in LDS as
+// 2 kSteerMaxRadius + 1 rows of kSteerPatchStride bytes; the offsets table reaches it as one dword per test, the two
+// samples' byte addresses in that patch (steer_pack_offsets: a1 | a2 << 16 of {drow1, dcol1, drow2, dcol2}).
+constexpr int kSteerMaxBins = 64;
+constexpr int kSteerMaxRadius = 15;   // of the moments' disc and of every offset component
+constexpr int kSteerMaxDir = 256;     // |dirs| component bound: 2 * 577,320 * 256 < 2^31
+constexpr int kSteerPatchStride = 40;
+struct SteerTables {
+    int n_bins, radius;
+    const int16_t* dirs;    // [n_bins][2] = (dcol, drow), device
+    const uint32_t* taddr;  // [n_bins][256], device
+};
+void steer_pack_offsets(const int8_t* offsets, int n_tests, uint32_t* out);  // host
+// Records + packed descriptors of kp_src[image][0 .. kp_count[image]) in keypoint order, as launch_brief writes them,
+// and per keypoint bin[image][max_kp] and moments[image][max_kp][2] = (m10, m01).  Reads no band list, no queue head.
+void launch_brief_steer(const uint8_t* blur, int n_images, int H, int W, const SteerTables& t, const int32_t* kp_src,
+                        const int32_t* kp_count, int max_kp, yv_keypoint* keypoints, Desc* desc, uint8_t* bin,
+                        int32_t* moments, hipStream_t s);
+// bin and moments alone of rc[0 .. min(*count, max_kp)) = {row, col}, any position of one H x W image
+void launch_orient(const uint8_t* blur, int H, int W, const SteerTables& t, const int32_t* rc, const int32_t* count,
+                   int max_kp, uint8_t* bin, int32_t* moments, hipStream_t s);
+
+// ---- matchers (yavo_match.hip, yavo_match_gate.hip) ----
 // The keypoint lists a matcher reads: slot i holds kp_count[i] points at desc / keypoints[i * max_kp].
 struct MatchLists {
     const Desc* desc;
@@ -101,6 +160,29 @@ struct MatchLists {
     const int32_t* kp_count;
     int max_kp;
 };
+// Brute-force Hamming NN: match_key[pair][q] = min over t of (dist << 16 | t).  max_train bounds every train
+// list's length (<= 2048: the FP4 matcher, otherwise the int8 +-1 form).  match_key2 != nullptr: also every query's
+// second-best key there (same format, 0xFFFFFFFF: no second train point), exact, first index on ties.
+void launch_match(const MatchLists& lists, const int32_t* pairs, int n_pairs, int max_train, uint32_t* match_key,
+                  uint32_t* match_key2, hipStream_t s);
+// The gated matcher (yv_match_gated / yv_batch_set_match_gates, yavo_match_gate.hip).  Per slot, the keypoints
+// bucketed by cell = (band of kGateBandRows rows, column >> col_shift): sorted[slot][max_kp] = {row | column << 16,
+// keypoint index} cell by cell, band_start[slot][n_bands + 1] = first entry of every band.  n_bands * kGateBandRows
+// covers every row, col_cells << col_shift every column, n_bands * col_cells <= kGateMaxCells; rows and columns are
+// 16-bit.
+constexpr int kGateBandRows = 32;
+constexpr int kGateMaxCells = 8192;
+constexpr int kGateMaxCoord = 65535;
+void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp, int n_bands,
+                      int col_cells, int col_shift, uint2* sorted, int32_t* band_start, hipStream_t s);
+// launch_match over the train points inside each pair's gate: gates[pair] = {drow_lo, drow_hi, dcol_lo, dcol_hi} on
+// train minus query position; mirror: the gate of the swapped pair list.  Writes a key for every query of every pair,
+// 0xFFFFFFFF where the gate holds no (second) train point.
+void launch_match_gated(const MatchLists& lists, const int32_t* pairs, int n_pairs, int n_bands, const uint2* sorted,
+                        const int32_t* band_start, const int32_t* gates, bool mirror, uint32_t* match_key,
+                        uint32_t* match_key2, hipStream_t s);
+
+// ---- match records (yavo_match_finalize.hip) ----
 // The finalize's outputs per pair: all records and the kept ones ([pair][max_kp]) with their counts, every query's
 // {distance, train index} and the removeOutliers limit.  match_pos != nullptr defers the two record lists: the finalize
 // then writes every query's position in the filtered list there ([pair][max_kp], -1: dropped) and leaves the lists to
@@ -114,11 +196,6 @@ struct MatchRecords {
     int32_t* match_lim;
     int32_t* match_pos;
 };
-// Brute-force Hamming NN: match_key[pair][q] = min over t of (dist << 16 | t).  max_train bounds every train
-// list's length (<= 2048: the FP4 matcher, otherwise the int8 +-1 form).  match_key2 != nullptr: also every query's
-// second-best key there (same format, 0xFFFFFFFF: no second train point), exact, first index on ties.
-void launch_match(const MatchLists& lists, const int32_t* pairs, int n_pairs, int max_train, uint32_t* match_key,
-                  uint32_t* match_key2, hipStream_t s);
 // The 2-NN match filter (yv_batch_set_match_filter; the values of YV_MATCH_RATIO / YV_MATCH_MUTUAL).
 constexpr int kMatchRatio = 1, kMatchMutual = 2;
 // ROBUST (the 2-NN match filter): also consumes the second-best keys and the reverse direction's keys (rev_key[pair][j]
@@ -145,59 +222,11 @@ void launch_match_finalize(uint32_t* match_key, const MatchLists& lists, const i
 // At most max_workgroups one-wave workgroups walk the lists.
 void launch_match_records(const MatchLists& lists, const int32_t* pairs, int n_pairs, const MatchRecords& out,
                           int max_workgroups, hipStream_t s);
-// The gated matcher (yv_match_gated / yv_batch_set_match_gates, yavo_match_gate.hip).  Per slot, the keypoints
-// bucketed by cell = (band of kGateBandRows rows, column >> col_shift): sorted[slot][max_kp] = {row | column << 16,
-// keypoint index} cell by cell, band_start[slot][n_bands + 1] = first entry of every band.  n_bands * kGateBandRows
-// covers every row, col_cells << col_shift every column, n_bands * col_cells <= kGateMaxCells; rows and columns are
-// 16-bit.
-constexpr int kGateBandRows = 32;
-constexpr int kGateMaxCells = 8192;
-constexpr int kGateMaxCoord = 65535;
-void launch_gate_sort(const yv_keypoint* keypoints, const int32_t* kp_count, int n_slots, int max_kp, int n_bands,
-                      int col_cells, int col_shift, uint2* sorted, int32_t* band_start, hipStream_t s);
-// launch_match over the train points inside each pair's gate: gates[pair] = {drow_lo, drow_hi, dcol_lo, dcol_hi} on
-// train minus query position; mirror: the gate of the swapped pair list.  Writes a key for every query of every pair,
-// 0xFFFFFFFF where the gate holds no (second) train point.
-void launch_match_gated(const MatchLists& lists, const int32_t* pairs, int n_pairs, int n_bands, const uint2* sorted,
-                        const int32_t* band_start, const int32_t* gates, bool mirror, uint32_t* match_key,
-                        uint32_t* match_key2, hipStream_t s);
-// Keypoint selection (yv_set_keypoint_select, yavo_select.hip): the filter between the detect kernel and launch_topk.
-// Suppression buckets the corners by tiles of kSelTileRows x kSelTileCols pixels, the quota by the caller's cells; both
-// grids have at most kSelMaxCells cells (the tiles of every accepted H x W do, the cells are the caller's to check).
-constexpr int kSelMaxCells = 8192;
-constexpr int kSelTileRows = 32, kSelTileCols = 64;
-constexpr int kSelMaxRadius = 8;
-constexpr int kSelMaxPerCell = 4096;
-constexpr int kSelMinCell = 8, kSelMaxCell = 8192;
-// Filters cand_keys[img][0 .. cand_count[img]) in place (nms_radius > 0: suppression; per_cell > 0: the quota) and does
-// launch_topk's bookkeeping for the detect kernel's list (cand_seen = corners before the filter, cand_count = 0).
-// scratch: n_images lists of cap keys; starts: [n_images][kSelMaxCells + 1]; counts: [2][n_images].  Returns the array
-// (inside counts) holding the filtered lists' lengths: launch_topk's cand_count, which resets it.
-uint32_t* launch_select(uint64_t* cand_keys, int64_t cap, uint32_t* cand_count, uint32_t* cand_seen, int n_images,
-                        int H, int W, int nms_radius, int cell_rows, int cell_cols, int per_cell, uint64_t* scratch,
-                        int32_t* starts, uint32_t* counts, hipStream_t s);
-// Rotation-steered BRIEF (yv_set_brief_steering, yavo_steer.hip): launch_brief's replacement while steering is on.
-// Every sample is the blurred image clamped to [0, H - 1] x [0, W - 1].  The kernel keeps a keypoint's patch in LDS as
-// 2 kSteerMaxRadius + 1 rows of kSteerPatchStride bytes; the offsets table reaches it as one dword per test, the two
-// samples' byte addresses in that patch (steer_pack_offsets: a1 | a2 << 16 of {drow1, dcol1, drow2, dcol2}).
-constexpr int kSteerMaxBins = 64;
-constexpr int kSteerMaxRadius = 15;   // of the moments' disc and of every offset component
-constexpr int kSteerMaxDir = 256;     // |dirs| component bound: 2 * 577,320 * 256 < 2^31
-constexpr int kSteerPatchStride = 40;
-struct SteerTables {
-    int n_bins, radius;
-    const int16_t* dirs;    // [n_bins][2] = (dcol, drow), device
-    const uint32_t* taddr;  // [n_bins][256], device
-};
-void steer_pack_offsets(const int8_t* offsets, int n_tests, uint32_t* out);  // host
-// Records + packed descriptors of kp_src[image][0 .. kp_count[image]) in keypoint order, as launch_brief writes them,
-// and per keypoint bin[image][max_kp] and moments[image][max_kp][2] = (m10, m01).  Reads no band list, no queue head.
-void launch_brief_steer(const uint8_t* blur, int n_images, int H, int W, const SteerTables& t, const int32_t* kp_src,
-                        const int32_t* kp_count, int max_kp, yv_keypoint* keypoints, Desc* desc, uint8_t* bin,
-                        int32_t* moments, hipStream_t s);
-// bin and moments alone of rc[0 .. min(*count, max_kp)) = {row, col}, any position of one H x W image
-void launch_orient(const uint8_t* blur, int H, int W, const SteerTables& t, const int32_t* rc, const int32_t* count,
-                   int max_kp, uint8_t* bin, int32_t* moments, hipStream_t s);
+// removeOutliers on externally supplied Matches records (one list).
+void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
+                           hipStream_t s);
+
+// ---- stereo refinement (yavo_stereo_subpix.hip) ----
 // Sub-pixel stereo refinement (yv_stereo_subpix / yv_batch_set_stereo_subpix, yavo_stereo_subpix.hip; the values of
 // YV_SUBPIX_*).  Images are read inside [image, image + (H - 1) * stride + W) only.
 constexpr int kSubpixNone = 0, kSubpixOk = 1, kSubpixOutside = 2, kSubpixEdge = 3;
@@ -217,9 +246,6 @@ void launch_subpix_batch(const uint8_t* images, int n_images, int H, int W, int 
                          const int32_t* kp_count, const int2* match_dj, const int32_t* match_lim,
                          const uint8_t* keep, int max_kp, int half_win, int search, const SubpixOut& out,
                          hipStream_t s);
-// removeOutliers on externally supplied Matches records (one list).
-void launch_filter_records(const yv_match* in, int n, int thr, yv_match* out, int32_t* out_count,
-                           hipStream_t s);
 
 // ---- geometry (yavo_geom.hip) ----
 // device workspace of launch_f_ransac: [n_lists][iters] hypotheses' F and inlier counts
@@ -235,29 +261,9 @@ void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, con
                     double* poses, uint8_t* outlier, int32_t* inliers, hipStream_t s);
 void launch_pose_gn(const int32_t* offsets, int n_problems, const double* X, const double* uv, const double* K,
                     double* poses, int32_t* iters, hipStream_t s);
-// cv::calcOpticalFlowPyrLK workspace view (yavo_lk.hip).  Level 0 is the caller's image; levels >= 1 live in
-// `pyr` ([image][pyr_pitch], level l at off[l], row stride ps[l] = w[l] rounded up to 64 bytes: every pyrDown store
-// is a whole aligned dword of full cache lines).  The tracker computes Scharr derivatives inside its windows; `der`
-// is one level's (dx, dy) int16 image for yv_lk_level only (ds[l] pixels per row = w[l] rounded up to 16).
-constexpr int kLkMaxLevels = 8;
-struct LkParams {
-    int levels = 0, win = 11, max_count = 30;
-    double eps2 = 1e-4, min_eig = 1e-3;
-    int h[kLkMaxLevels] = {}, w[kLkMaxLevels] = {};
-    int ps[kLkMaxLevels] = {}, ds[kLkMaxLevels] = {};
-    int64_t off[kLkMaxLevels] = {};
-    const uint8_t* img0 = nullptr;
-    int stride0 = 0;
-    int64_t pitch0 = 0;
-    uint8_t* pyr = nullptr;
-    int64_t pyr_pitch = 0;
-    int16_t* der = nullptr;
-    int64_t der_pitch = 0;  // int16 elements of `der`
-};
-void launch_lk_pyramid(const LkParams& P, int n_images, hipStream_t s);
-void launch_lk_derivs(const LkParams& P, int image, int level, int16_t* der, hipStream_t s);
-void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const float* pts, const int32_t* counts,
-                     int pts_stride, int max_pts, float* next_pts, uint8_t* status, float* err, hipStream_t s);
+void launch_track_pose(int n_tracks, const int32_t* edge_count, int stride, const double* edge_X,
+                       const double* edge_uv, const double* K, const double* priors, double* poses,
+                       uint8_t* edge_outlier, int32_t* inliers, hipStream_t s);
 
 // ---- track composition (yavo_track.hip): a run's stereo and temporal matches into the pose LM's edges ----
 // What the track kernels read: the run's pair list, keypoints ([slot][max_kp]) and match records ([pair][max_kp]), the
@@ -300,6 +306,32 @@ void launch_stereo_points(const int32_t* stereo_pairs, int n_tracks, const Track
 void launch_lk_edges(int n_tracks, const PointsOut& pts, const float* next, const uint8_t* status, int max_kp,
                      const EdgeOut& out, hipStream_t s);
 
+// ---- Lucas-Kanade (yavo_lk.hip) ----
+// cv::calcOpticalFlowPyrLK workspace view (yavo_lk.hip).  Level 0 is the caller's image; levels >= 1 live in
+// `pyr` ([image][pyr_pitch], level l at off[l], row stride ps[l] = w[l] rounded up to 64 bytes: every pyrDown store
+// is a whole aligned dword of full cache lines).  The tracker computes Scharr derivatives inside its windows; `der`
+// is one level's (dx, dy) int16 image for yv_lk_level only (ds[l] pixels per row = w[l] rounded up to 16).
+constexpr int kLkMaxLevels = 8;
+struct LkParams {
+    int levels = 0, win = 11, max_count = 30;
+    double eps2 = 1e-4, min_eig = 1e-3;
+    int h[kLkMaxLevels] = {}, w[kLkMaxLevels] = {};
+    int ps[kLkMaxLevels] = {}, ds[kLkMaxLevels] = {};
+    int64_t off[kLkMaxLevels] = {};
+    const uint8_t* img0 = nullptr;
+    int stride0 = 0;
+    int64_t pitch0 = 0;
+    uint8_t* pyr = nullptr;
+    int64_t pyr_pitch = 0;
+    int16_t* der = nullptr;
+    int64_t der_pitch = 0;  // int16 elements of `der`
+};
+void launch_lk_pyramid(const LkParams& P, int n_images, hipStream_t s);
+void launch_lk_derivs(const LkParams& P, int image, int level, int16_t* der, hipStream_t s);
+void launch_lk_track(const LkParams& P, const int32_t* pairs, int n_pairs, const float* pts, const int32_t* counts,
+                     int pts_stride, int max_pts, float* next_pts, uint8_t* status, float* err, hipStream_t s);
+
+// ---- essential matrix (yavo_essential.hip) ----
 // cv::findEssentialMat (RANSAC) + cv::recoverPose (yavo_essential.hip).  Workspace of a yv_essential.
 // RANSAC iterations evaluated per round: 64, or 1024 (>= findEssentialMat's 1000) for workspaces of at most kEssWidePairs
 // lists, where the chip is otherwise idle: a list that needs all its iterations (the LoopHandler's re-initialisation
@@ -332,6 +364,9 @@ struct EssRun {
     double focal, ppx, ppy, prob, threshold;
     int max_iters;
 };
+struct Mat3 {
+    double v[9];
+};
 void launch_find_essential(const EssParams& P, const EssRun& r, const float* pts1, const float* pts2,
                            const int32_t* counts, int n_pairs, int pts_stride, double* E, uint8_t* mask,
                            int32_t* found, int32_t* stats, hipStream_t s);
@@ -339,16 +374,11 @@ void launch_find_essential(const EssParams& P, const EssRun& r, const float* pts
 // five-point subsets q1 / q2 [n_sets][5][2]; models [n_sets][10][9] (zeros past a subset's count), nmod [n_sets]
 int launch_debug_ess_models(const EssParams& P, const double* q1, const double* q2, int n_sets, double* models,
                             int32_t* nmod, hipStream_t s);
-struct Mat3 {
-    double v[9];
-};
-// the context's device / stream for the host-side modules that do not see yv_ctx (yavo_io.hip); defined with the
-// context, beside yv_create in yavo_api.hip
-int ctx_device(struct ::yv_ctx* ctx);
-hipStream_t ctx_stream(struct ::yv_ctx* ctx);
 void launch_recover_pose(const EssParams& P, const double* E, const float* pts1, const float* pts2,
                          const int32_t* counts, int n_pairs, int pts_stride, const Mat3& K, double* R, double* t,
                          int32_t* good, hipStream_t s);
+
+// ---- bundle adjustment (yavo_ba.hip) ----
 // sliding-window BA (yavo_ba.hip): the device graph, workspace and estimate of a yv_ba
 struct BaParams {
     int P = 0, nf = 0, np = 0, ns = 0, L = 0, E = 0;
@@ -416,11 +446,13 @@ void launch_ba_chi2(const BaParams& P, const BaMat3& K, hipStream_t s);
 void launch_ba_finish(const BaParams& P, hipStream_t s);
 void launch_ba_ctl_resume(BaCtl* c, hipStream_t s);
 
+// ---- map (yavo_map.hip) ----
 // the shared map (yavo_map.hip): one chunk's block after its pose LM
 void launch_map_chunk(const double* rel, int n, int64_t first_frame, int kf_every, const int32_t* edge_count,
                       const double* edge_X, const uint8_t* edge_outlier, int max_kp, int max_kf, void* block,
                       hipStream_t s);
 
+// ---- PNG (yavo_inflate.hip) ----
 // PNG decoding on the GPU (yavo_inflate.hip): per-image status codes and the two kernels
 enum : int32_t {
     kPngOk = 0, kPngErrHeader = 1, kPngErrBlock = 2, kPngErrCode = 3, kPngErrOverrun = 4, kPngErrShort = 5,
@@ -444,8 +476,10 @@ void launch_png_inflate(const uint8_t* src, const int64_t* off, const int32_t* l
 void launch_png_unfilter(const uint8_t* raw, int64_t raw_pitch, int n, int H, int W, uint8_t* dst, int64_t dst_pitch,
                          int dst_stride, int32_t* status, const uint32_t* adler, uint32_t* bad_total, hipStream_t s);
 
-void launch_track_pose(int n_tracks, const int32_t* edge_count, int stride, const double* edge_X,
-                       const double* edge_uv, const double* K, const double* priors, double* poses,
-                       uint8_t* edge_outlier, int32_t* inliers, hipStream_t s);
+// ---- context (yavo_api.hip) ----
+// the context's device / stream for the host-side modules that do not see yv_ctx (yavo_io.hip); defined with the
+// context, beside yv_create in yavo_api.hip
+int ctx_device(struct ::yv_ctx* ctx);
+hipStream_t ctx_stream(struct ::yv_ctx* ctx);
 
 }  // namespace yavo

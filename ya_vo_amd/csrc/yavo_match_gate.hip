@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "yavo_internal.h"
+#include "yavo_wave.h"
 
 namespace yavo {
 
@@ -56,24 +57,8 @@ __global__ __launch_bounds__(GS_NT) void gate_sort_kernel(const yv_keypoint* __r
         }
     }
     __syncthreads();
-    // exclusive scan over the cells: GS_PER consecutive cells per thread, then the threads' sums
-    int local[GS_PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < GS_PER; ++k) {
-        const int c = tid * GS_PER + k;
-        local[k] = sum;
-        sum += c < n_cells ? s_cell[c] : 0;
-    }
-    int incl = sum;
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();  // every count is read, every wave total written
-    int base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
+    int local[GS_PER];
+    const int base = cell_excl_scan<GS_NT, GS_PER>(s_cell, n_cells, s_wave, local);
 #pragma unroll
     for (int k = 0; k < GS_PER; ++k) {
         const int c = tid * GS_PER + k;

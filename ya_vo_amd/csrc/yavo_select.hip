@@ -13,6 +13,7 @@
 #include <algorithm>
 
 #include "yavo_internal.h"
+#include "yavo_wave.h"
 
 namespace yavo {
 
@@ -65,24 +66,8 @@ __global__ __launch_bounds__(SB_NT) void select_bucket_kernel(const uint64_t* __
     for (int i = tid; i < n; i += SB_NT)
         atomicAdd(&s_cell[cell_of(in[i], (uint32_t)W, (uint32_t)cell_rows, (uint32_t)cell_cols, cells_x, n_cells)], 1);
     __syncthreads();
-    // exclusive scan over the cells: SB_PER consecutive cells per thread, then the threads' sums
-    int local[SB_PER], sum = 0;
-#pragma unroll
-    for (int k = 0; k < SB_PER; ++k) {
-        const int c = tid * SB_PER + k;
-        local[k] = sum;
-        sum += c < n_cells ? s_cell[c] : 0;
-    }
-    int incl = sum;
-    const int lane = tid & 63, wave = tid >> 6;
-    for (int off = 1; off < 64; off <<= 1) {
-        const int o = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += o;
-    }
-    if (lane == 63) s_wave[wave] = incl;
-    __syncthreads();  // every count is read, every wave total written
-    int base = incl - sum;
-    for (int w = 0; w < wave; ++w) base += s_wave[w];
+    int local[SB_PER];
+    const int base = cell_excl_scan<SB_NT, SB_PER>(s_cell, n_cells, s_wave, local);
 #pragma unroll
     for (int k = 0; k < SB_PER; ++k) {
         const int c = tid * SB_PER + k;

@@ -1,7 +1,7 @@
 // yavo_steer.hip -- rotation-steered BRIEF (yv_set_brief_steering): the keypoint's orientation
 // bin from the intensity centroid of its blurred patch, then the 256 tests of that bin's rotated pattern.  Integer
 // only.  Every sample is S(r, c) = blurred[clamp(r, 0, H - 1)][clamp(c, 0, W - 1)]: no padding column, no column W,
-// no row H, nothing out of bounds.  brief_kernel (yavo_kernels.hip) stays the path with steering off.
+// no row H, nothing out of bounds.  brief_kernel (yavo_brief.hip) stays the path with steering off.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
