@@ -1,4 +1,4 @@
-"""GPU parity of the sliding-window bundle adjustment (yv_ba, ya_vo_amd/csrc/yavo_ba.hip; BASELINE.json config 5)
+"""GPU parity of the sliding-window bundle adjustment (yv_ba, ya_vo_amd/csrc/yavo_ba*.hip; BASELINE.json config 5)
 with the CPU oracle (oracle/yavo_oracle_ba.c or_ba_lm): poses, landmarks, the chi2 log and the iteration count, bit
 for bit, from small windows to the config-5 size (20 keyframes, 10k landmarks, 5 observations each)."""
 import numpy as np

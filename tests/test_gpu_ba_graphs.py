@@ -1,4 +1,4 @@
-"""GPU parity of the bundle adjustment (yv_ba, ya_vo_amd/csrc/yavo_ba.hip) with the CPU oracle (or_ba_lm, mode 0) on
+"""GPU parity of the bundle adjustment (yv_ba, ya_vo_amd/csrc/yavo_ba*.hip) with the CPU oracle (or_ba_lm, mode 0) on
 what scene.ba_window never produces: general graphs (shuffled edges, duplicates, poses and landmarks without edges,
 single-edge landmarks, landmarks on fixed poses only), a K whose every entry matters, sums that wrap the tree4096 and
 landmark-block leaves, ticket groups above 16 workgroups, and the LM control's stop arms on the device, in the host

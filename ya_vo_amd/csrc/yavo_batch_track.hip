@@ -2,7 +2,7 @@
 // yv_batch_set_tracks and the track group's buffers, yv_batch_track (the edge build from the matches or through LK,
 // then the pose LM and the map block) and the streams and events that let them overlap the next run: the build
 // stream, the side stream of the LM, the LM deferred into the next run.  Host code only; the kernels are in
-// yavo_track.hip, yavo_geom.hip, yavo_lk.hip and yavo_map.hip.
+// yavo_track.hip, yavo_pose.hip, yavo_lk.hip and yavo_map.hip.
 #include "yavo_host.h"
 
 #include <cstdlib>

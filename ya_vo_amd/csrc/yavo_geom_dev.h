@@ -1,11 +1,12 @@
-// yavo_geom_dev.h -- device functions the geometry kernels (yavo_geom.hip) and the track kernels (yavo_track.hip)
-// share: the workgroup scan of their compactions and the triangulation of one match (Eigen JacobiSVD on the 4x4 DLT
-// system, in registers).  Every floating-point expression is written in the reference's operation order; both files are
-// built with -ffp-contract=off.
+// yavo_geom_dev.h -- device functions the geometry kernels (yavo_geom.hip), the pose kernels (yavo_pose.hip) and the
+// track kernels (yavo_track.hip) share: the workgroup scan of their compactions, a wave-uniform double in SGPRs and the
+// triangulation of one match (Eigen JacobiSVD on the 4x4 DLT system, in registers).  Every floating-point expression is
+// written in the reference's operation order; the files are built with -ffp-contract=off.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stdint.h>
 
 #include "yavo_se3.h"
 
@@ -36,6 +37,13 @@ __device__ int block_excl_scan_geom(int v, int* s_tmp, int* total) {
     __syncthreads();
     if (total) *total = tot;
     return base + incl - v;
+}
+
+// a wave-uniform double (the value of lane 0) in SGPRs
+__device__ __forceinline__ double uni_f64(double v) {
+    const uint64_t b = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+    return __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
 }
 
 // a Jacobi rotation of the SVD below

@@ -1,7 +1,8 @@
 // yavo_host.h -- what the host side of the C ABI shares between its translation units (yavo_api.hip, yavo_batch.hip,
-// yavo_batch_track.hip, yavo_geom_host.hip and the ABI parts of yavo_lk.hip, yavo_essential.hip, yavo_ba.hip): error
-// handling, the owner of what the HIP runtime hands out, the context and the batch, and the context's two host staging
-// mechanisms.  Host code only: nothing here is passed to a kernel.
+// yavo_batch_track.hip, yavo_geom_host.hip, yavo_ba_host.hip, yavo_ba_window.hip and the ABI parts of yavo_lk.hip,
+// yavo_essential.hip, yavo_ba_ldlt.hip): error handling, the owner of what the HIP runtime hands out, the context, the
+// batch and the bundle adjustment's workspace, and the context's two host staging mechanisms.  Host code only: nothing
+// here is passed to a kernel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -490,5 +491,50 @@ struct EdgeSlice {
     int32_t* inliers;
 };
 EdgeSlice edge_slice(const yv_batch* b, int k);
+
+}  // namespace yavo
+
+// ---- bundle adjustment (yavo_ba_host.hip), as the sliding window (yavo_ba_window.hip) needs it ----
+struct yv_ba {
+    yv_ctx* ctx = nullptr;
+    int dev = 0;
+    hipStream_t st = nullptr;
+    hipStream_t ctx_st = nullptr;  // the context's stream (yv_ba_set_stream(b, NULL) returns to it)
+    int max_poses = 0, max_landmarks = 0, max_edges = 0;
+    int64_t cv_cap = 0;
+    yavo::BaParams P;
+    yavo::Mat3 K{};
+    yavo::HipOwned mem;  // every d_* / h_* buffer below and P's
+    int32_t *d_ep = nullptr, *d_el = nullptr, *d_pe_off = nullptr, *d_pe = nullptr, *d_le_off = nullptr,
+            *d_le = nullptr, *d_cv_off = nullptr, *d_cv_e1 = nullptr, *d_cv_e2 = nullptr;
+    double* d_meas = nullptr;
+    int* d_cur = nullptr;          // the state the estimate is in (BaParams::cur)
+    unsigned* d_ticket = nullptr;  // last-workgroup counters [kBaTickets]
+    int64_t schur_cap = 0;         // Schur tasks P.spart / P.sticket hold
+    unsigned long long* d_maxdiag = nullptr;
+    double* h_scal = nullptr;  // pinned [4]
+    yavo::BaCtl* d_ctl = nullptr;  // the device-driven LM's control block
+    yavo::BaCtl* h_ctl = nullptr;  // pinned copy
+    double* h_log = nullptr;       // pinned copy of d_log [log_cap]
+    bool resumed = false;          // the last ba_solve_wait resumed a suspended solve
+    int resumes = 0;               // suspended trial loops resumed since creation (yv_ba_debug_resumes)
+    double* d_log = nullptr;       // [log_cap] chi2 per iteration
+    int log_cap = 0;
+    int device_control = 1;        // yv_ba_set_control
+    bool ready = false;
+};
+
+namespace yavo {
+
+// the global-memory LDLT keeps 2 x 6 np doubles in dynamic LDS beside ~3 KB of its own: 6 x 640 rows fit 64 KB
+constexpr int kBaMaxPoses = 640;
+
+// the tree4096 class totals and per-sum counters of np free poses: P.spart / P.sticket for the Schur tasks (nb upper
+// blocks + np b_schur rows), P.rpart / P.rticket for the pose reduce; grown on demand
+int ba_ensure_schur(yv_ba* b, int np, hipStream_t st);
+// The LM of yv_ba_solve with its control on the device, in two halves (see yavo_ba_host.hip).  poses / landmarks: host
+// in / out; both nullptr: the problem's poses and landmarks are already in P.poses / P.X on the device and stay there.
+int ba_solve_enqueue(yv_ba* b, const double* poses, const double* landmarks, int max_iters);
+int ba_solve_wait(yv_ba* b, double* poses, double* landmarks, int max_iters, double* chi2_log, int* iters);
 
 }  // namespace yavo

@@ -57,6 +57,9 @@ __device__ __forceinline__ int xcd_swizzle(int b, int nblocks) {
 struct Desc {                      // 256-bit BRIEF descriptor, test j -> bit j (LSB-first bytes)
     uint32_t w[8];
 };
+struct Mat3 {                      // a row-major 3 x 3 (a camera's K) as a kernel argument: recoverPose, the BA
+    double v[9];
+};
 
 // ---- detect (yavo_detect.hip) ----
 // FAST-12 candidate test + Harris response, appends (response, index) keys per image.  eig: the cv::eigen
@@ -247,7 +250,7 @@ void launch_subpix_batch(const uint8_t* images, int n_images, int H, int W, int 
                          const uint8_t* keep, int max_kp, int half_win, int search, const SubpixOut& out,
                          hipStream_t s);
 
-// ---- geometry (yavo_geom.hip) ----
+// ---- geometry (yavo_geom.hip): F-RANSAC, triangulation, world2Camera ----
 // device workspace of launch_f_ransac: [n_lists][iters] hypotheses' F and inlier counts
 size_t f_ransac_ws_bytes(int n_lists, int iters);
 void launch_f_ransac(const yv_match* matches, int64_t list_stride, const int32_t* counts, int n_lists,
@@ -257,6 +260,8 @@ void launch_f_ransac(const yv_match* matches, int64_t list_stride, const int32_t
 void launch_triangulate(const yv_match* m, int n, const double* poses2, const double* K, double* Xw, uint8_t* ok,
                         int32_t* n_ok, hipStream_t s, const int32_t* dcol_q8 = nullptr);
 void launch_world2camera(const double* X, int n, const double* T, const double* K, double* out, hipStream_t s);
+
+// ---- pose-only LM and GN (yavo_pose.hip) ----
 void launch_pose_lm(const int32_t* offsets, int n_problems, const double* X, const double* uv, const double* K,
                     double* poses, uint8_t* outlier, int32_t* inliers, hipStream_t s);
 void launch_pose_gn(const int32_t* offsets, int n_problems, const double* X, const double* uv, const double* K,
@@ -364,9 +369,6 @@ struct EssRun {
     double focal, ppx, ppy, prob, threshold;
     int max_iters;
 };
-struct Mat3 {
-    double v[9];
-};
 void launch_find_essential(const EssParams& P, const EssRun& r, const float* pts1, const float* pts2,
                            const int32_t* counts, int n_pairs, int pts_stride, double* E, uint8_t* mask,
                            int32_t* found, int32_t* stats, hipStream_t s);
@@ -378,8 +380,18 @@ void launch_recover_pose(const EssParams& P, const double* E, const float* pts1,
                          const int32_t* counts, int n_pairs, int pts_stride, const Mat3& K, double* R, double* t,
                          int32_t* good, hipStream_t s);
 
-// ---- bundle adjustment (yavo_ba.hip) ----
-// sliding-window BA (yavo_ba.hip): the device graph, workspace and estimate of a yv_ba
+// ---- bundle adjustment (yavo_ba.hip, yavo_ba_ldlt.hip; the host side: yavo_ba_host.hip, yavo_ba_window.hip) ----
+namespace ba {
+// what the kernels and the host's buffer sizes share
+constexpr int kNT = 256;             // lanes of a landmark-block workgroup (ba_step_kernel, ba_chi2_kernel)
+constexpr int kTicketGroups = 64;    // counters of a large grid's last-workgroup ticket (ba_last_block_h)
+constexpr int kWLeaves = 4096;       // leaves of a tree4096 sum (yavo_ba.hip wide_local_tree)
+// 16 workgroups of 256 lanes per sum (32 x 128 until c49: the reduce kernel 19.4 -> 17.3 us, the Schur kernel the same;
+// 8 x 512: Schur 33 us, profiles/r05/c49)
+constexpr int kWG = 16;
+constexpr int kWLanes = kWLeaves / kWG;  // 256
+}  // namespace ba
+// sliding-window BA: the device graph, workspace and estimate of a yv_ba
 struct BaParams {
     int P = 0, nf = 0, np = 0, ns = 0, L = 0, E = 0;
     const int32_t* ep = nullptr;      // [E]
@@ -434,17 +446,17 @@ struct BaCtl {
     int q, it, stop, iters;
     int skip_iter, skip_trial, suspended, iter_done;
 };
-struct BaMat3 {
-    double v[9];
-};
 // linearise + the H / b blocks (first: the largest diagonal into *P.maxdiag; device control: the iteration begins)
-void launch_ba_linearize(const BaParams& P, const BaMat3& K, int first, hipStream_t s);
+void launch_ba_linearize(const BaParams& P, const Mat3& K, int first, hipStream_t s);
 // one damping trial: Dinv / W, Schur, LDLT, step into the trial state, chi2 + scale (device control: the decision)
-void launch_ba_trial(const BaParams& P, const BaMat3& K, double lambda, hipStream_t s);
+void launch_ba_trial(const BaParams& P, const Mat3& K, double lambda, hipStream_t s);
 // the solve's first chi2 (device control: the control block's initialisation)
-void launch_ba_chi2(const BaParams& P, const BaMat3& K, hipStream_t s);
+void launch_ba_chi2(const BaParams& P, const Mat3& K, hipStream_t s);
 void launch_ba_finish(const BaParams& P, hipStream_t s);
 void launch_ba_ctl_resume(BaCtl* c, hipStream_t s);
+// Eigen's LDLT on the reduced pose system P.S x = P.bs into P.xp, P.scal[2] = isPositive (yavo_ba_ldlt.hip; part of
+// launch_ba_trial, alone behind yv_ba_debug_ldlt)
+void launch_ba_ldlt(const BaParams& P, hipStream_t s);
 
 // ---- map (yavo_map.hip) ----
 // the shared map (yavo_map.hip): one chunk's block after its pose LM

@@ -1,6 +1,6 @@
 // yavo_se3.h -- device restatements of the Sophus SE3d operations the geometry kernels share (pose = SE3d::data()
 // = {qx, qy, qz, qw, tx, ty, tz}): Eigen quaternion product / rotation / toRotationMatrix, SE3 act / mul (with
-// Sophus' renormalisation) and SE3::exp with fdlibm's sin / cos kernels (oracle/yavo_oracle_geom.c: or_se3_*).
+// Sophus' renormalisation) / inverse and SE3::exp with fdlibm's sin / cos kernels (oracle/yavo_oracle_geom.c: or_se3_*).
 // Every expression in the oracle's order; files are built with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -159,6 +159,31 @@ __device__ __forceinline__ void se3_mul(const double* A, const double* B, double
     }
     out[0] = q[0]; out[1] = q[1]; out[2] = q[2]; out[3] = q[3];
     out[4] = t0; out[5] = t1; out[6] = t2;
+}
+
+// Sophus SE3d::inverse on data() = {qx, qy, qz, qw, tx, ty, tz}: SO3(q*) renormalised, -t rotated as Eigen's
+// Quaternion * Vector3 (uv = 2 (q.vec x v); v + w uv + q.vec x uv): or_se3_inverse / ya_vo_amd/sequence.py
+// se3_inverse, operation for operation (no contraction: -ffp-contract=off; sqrt and / correctly rounded)
+__device__ void se3_inverse(const double* T, double* o) {
+    double x = -T[0], y = -T[1], z = -T[2], w = T[3];
+    const double len = sqrt((x * x + z * z) + (y * y + w * w));  // the SO3 constructor's normalisation
+    x = x / len;
+    y = y / len;
+    z = z / len;
+    w = w / len;
+    const double vx = T[4] * -1.0, vy = T[5] * -1.0, vz = T[6] * -1.0;
+    double ux = y * vz - z * vy, uy = z * vx - x * vz, uz = x * vy - y * vx;
+    ux += ux;
+    uy += uy;
+    uz += uz;
+    const double cx = y * uz - z * uy, cy = z * ux - x * uz, cz = x * uy - y * ux;
+    o[0] = x;
+    o[1] = y;
+    o[2] = z;
+    o[3] = w;
+    o[4] = vx + w * ux + cx;
+    o[5] = vy + w * uy + cy;
+    o[6] = vz + w * uz + cz;
 }
 
 __device__ void se3_exp(const double* a, double* out) {

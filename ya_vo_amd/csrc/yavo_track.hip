@@ -1,5 +1,5 @@
 // yavo_track.hip -- gfx950 kernels of the track composition: a run's stereo and temporal matches into the PnP edges
-// that the per-frame pose LM (yavo_geom.hip, launch_track_pose) solves.
+// that the per-frame pose LM (yavo_pose.hip, launch_track_pose) solves.
 //
 //   track_build_kernel    match mode: temporal match -> stereo match -> triangulated point, one edge each
 //   stereo_points_kernel  LK mode (trackLastFrame, src/LoopHandler.cc:298-454): frame k-1's stereo map points

@@ -31,7 +31,7 @@ def se3_inverse(T) -> np.ndarray:
     """Sophus SE3d::inverse on data() = {qx, qy, qz, qw, tx, ty, tz}: SO3(q*) (renormalised by the SO3 constructor,
     |q| summed as Eigen's squaredNorm pairs it) and that rotation applied to -t as Eigen's Quaternion * Vector3 does
     (uv = 2 (q.vec x v); v + w uv + q.vec x uv) -- oracle/yavo_oracle_geom.c or_se3_inverse's arithmetic, in scalar
-    IEEE doubles, which the device restatement (yavo_ba.hip se3_inverse_dev, no contraction) repeats bit for bit."""
+    IEEE doubles, which the device restatement (yavo_se3.h se3_inverse, no contraction) repeats bit for bit."""
     x, y, z, w = -float(T[0]), -float(T[1]), -float(T[2]), float(T[3])
     n = math.sqrt((x * x + z * z) + (y * y + w * w))
     x, y, z, w = x / n, y / n, z / n, w / n
@@ -108,7 +108,7 @@ def apply_window(records: Dict[int, FrameRecord], frames: List[int], poses: np.n
             base += n
 
 
-# poses of one device BA window (yv_ba_window_solve, yavo_ba.hip kWinMaxPoses)
+# poses of one device BA window (yv_ba_window_solve, yavo_ba_window.hip kWinMaxPoses)
 WINDOW_MAX_POSES = 128
 
 
