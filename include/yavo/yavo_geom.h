@@ -248,6 +248,28 @@ int yv_ba_window_trajectory(yv_ba_window* w, int64_t first, int n, double* T_wc)
  * sequence's frame-sharded form (ya_vo_amd.sequence.SequenceShard). */
 int yv_ba_window_export_block(yv_ba_window* w, int64_t first, int n, int64_t chunk_frame, int64_t frame_id_offset,
                               void* d_block, int max_kf, int lm_stride, void* stream);
+/* ---- the window's multi-view mode (off by default; ya_vo_amd/sequence.py window_problem_tracks) ----
+ * A landmark the temporal matches follow over several frames enters the window once, observed by every frame of its
+ * chain, instead of once per frame with two observations.  Record l of frame k carries query = edge_query[k][e] (its
+ * keypoint in L_{k-1}) and train = match_dj[2 k][query][1] (in L_k); its parent is the record of frame k-1 with the
+ * smallest index whose train is this query, within the window and not at the window's second pose (chains are cut at
+ * the window's start).  A chain rooted at window pose a with m records is one landmark with m + 1 edges in pose order
+ * (a-1: the root's uv_prev; a .. a+m-1: the records' uv_own) and the root's X; landmarks ascend by (a, m, root's
+ * index), edges are landmark-major; every record of a chain takes the landmark's refined X.  Results are
+ * bit-identical to the host assembly + yv_ba_set_problem / yv_ba_solve.  The co-visibility lists are sized for a full
+ * window (max_lm (n (n + 1) / 2 + n) entries for n poses) when the window first reaches a length, never after.
+ * YV_ERR_INVALID while a solve is pending, or when frames were recorded with the other setting. */
+int yv_ba_window_set_multiview(yv_ba_window* w, int on);
+/* yv_ba_window_add_block that also records the links: d_match_dj = the batch's match_dj ([pairs][dj_stride][2] i32
+ * {distance, train index}, temporal pairs at even indices), dj_stride >= max_kp.  With the mode on it is the only
+ * way to add (NULL d_match_dj, or max_kp above the window's max_lm: YV_ERR_INVALID); with it off the two extra
+ * arguments are ignored. */
+int yv_ba_window_add_block_linked(yv_ba_window* w, const void* d_block, int64_t first_frame, int n_frames,
+                                  const double* d_edge_uv, const int32_t* d_edge_query, const void* d_matches,
+                                  int max_kp, const int32_t* d_match_dj, int64_t dj_stride, void* stream);
+/* one frame's links (host, blocking, multi-view only): up to cap of query / train / parent (-1: none; any may be
+ * NULL), in the record order of yv_ba_window_read */
+int yv_ba_window_read_links(yv_ba_window* w, int64_t frame, int32_t* query, int32_t* train, int32_t* parent, int cap);
 
 #ifdef __cplusplus
 }

@@ -170,6 +170,9 @@ GEOM_SIGNATURES = {
     "yv_ba_window_destroy": (None, [_P]),
     "yv_ba_window_reserve": (_I, [_P, ctypes.c_int64]),
     "yv_ba_window_add_block": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P, _I, _P]),
+    "yv_ba_window_set_multiview": (_I, [_P, _I]),
+    "yv_ba_window_add_block_linked": (_I, [_P, _P, ctypes.c_int64, _I, _P, _P, _P, _I, _P, ctypes.c_int64, _P]),
+    "yv_ba_window_read_links": (_I, [_P, ctypes.c_int64, _P, _P, _P, _I]),
     "yv_ba_window_solve": (_I, [_P, ctypes.c_int64, _I, _I, _P, _I, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
     "yv_ba_window_solve_begin": (_I, [_P, ctypes.c_int64, _I, _I, _P, _I, _P]),
     "yv_ba_window_solve_end": (_I, [_P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
@@ -1006,8 +1009,21 @@ class BaWindow:
         """Size the record store for n_frames frames up front (yv_ba_window_reserve: no growth inside the loop)."""
         _check(self.lib.yv_ba_window_reserve(self.handle, int(n_frames)), "yv_ba_window_reserve")
 
+    def set_multiview(self, on: bool) -> None:
+        """Landmarks followed over several frames enter the window once (yv_ba_window_set_multiview); before the
+        first add_block."""
+        _check(self.lib.yv_ba_window_set_multiview(self.handle, 1 if on else 0), "yv_ba_window_set_multiview")
+
     def add_block(self, d_block: int, first_frame: int, n_frames: int, d_edge_uv: int, d_edge_query: int,
-                  d_matches: int, max_kp: int, stream: int = 0) -> None:
+                  d_matches: int, max_kp: int, stream: int = 0, d_match_dj: int = 0, dj_stride: int = 0) -> None:
+        """d_match_dj (the batch view's match_dj, pair stride dj_stride keypoints, default max_kp): the links of the
+        multi-view mode (yv_ba_window_add_block_linked)."""
+        if d_match_dj:
+            _check(self.lib.yv_ba_window_add_block_linked(
+                self.handle, ctypes.c_void_p(d_block), first_frame, n_frames, ctypes.c_void_p(d_edge_uv),
+                ctypes.c_void_p(d_edge_query), ctypes.c_void_p(d_matches), max_kp, ctypes.c_void_p(d_match_dj),
+                dj_stride or max_kp, ctypes.c_void_p(stream) if stream else None), "yv_ba_window_add_block_linked")
+            return
         _check(self.lib.yv_ba_window_add_block(self.handle, ctypes.c_void_p(d_block), first_frame, n_frames,
                                                ctypes.c_void_p(d_edge_uv), ctypes.c_void_p(d_edge_query),
                                                ctypes.c_void_p(d_matches), max_kp,
@@ -1050,6 +1066,17 @@ class BaWindow:
                                           _ptr(up), self.max_lm), "yv_ba_window_read")
         k = n.value
         return T, e[:k].copy(), X[:k].copy(), uo[:k].copy(), up[:k].copy()
+
+    def read_links(self, frame: int):
+        """-> (query [n], train [n], parent [n]; -1: none) of a frame's records (multi-view mode)"""
+        q, t, p = (np.zeros(self.max_lm, np.int32) for _ in range(3))
+        n = ctypes.c_int(0)
+        _check(self.lib.yv_ba_window_read(self.handle, frame, None, ctypes.byref(n), None, None, None, None, 0),
+               "yv_ba_window_read")
+        _check(self.lib.yv_ba_window_read_links(self.handle, frame, _ptr(q), _ptr(t), _ptr(p), self.max_lm),
+               "yv_ba_window_read_links")
+        k = n.value
+        return q[:k].copy(), t[:k].copy(), p[:k].copy()
 
     def trajectory(self, first: int, n: int) -> np.ndarray:
         T = np.zeros((n, 7))

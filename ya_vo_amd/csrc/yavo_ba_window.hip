@@ -1,8 +1,9 @@
 // yavo_ba_window.hip -- the sliding BA window of the chained stereo front end, assembled on the device
 // (ya_vo_amd/sequence.py window_problem / apply_window / frame_records_from_block, restated): frame records in HBM, the
 // graph's index arrays from per-frame counts (every landmark is seen by its own frame and the one before), no host
-// round trip.  The yv_ba_window C ABI (include/yavo/yavo_geom.h); the solve itself is the yv_ba's (yavo_host.h:
-// ba_ensure_schur, ba_solve_enqueue, ba_solve_wait of yavo_ba_host.hip).
+// round trip.  The multi-view mode (landmarks followed over several frames enter the window once; its kernels are
+// yavo_ba_window_tracks.hip's) is switched here.  The yv_ba_window C ABI (include/yavo/yavo_geom.h); the solve itself
+// is the yv_ba's (yavo_host.h: ba_ensure_schur, ba_solve_enqueue, ba_solve_wait of yavo_ba_host.hip).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -220,7 +221,8 @@ struct yv_ba_window {
     int64_t hint = 0;          // yv_ba_window_reserve: frames the store is first sized for
     double *d_T = nullptr, *d_X = nullptr, *d_uvo = nullptr, *d_uvp = nullptr;
     int32_t *d_cnt = nullptr, *d_edge = nullptr;
-    int64_t* d_info = nullptr;  // [1 + 2 max_kf]: n_kf, (frame, count) per keyframe of the last block
+    int64_t* d_info = nullptr;  // [1 + 3 max_kf]: n_kf, (frame, count) per keyframe of the last block, then (multi-view)
+                                // the keyframes' root counts
     int64_t* h_info = nullptr;  // pinned copy
     yavo::HipOwned mem;         // the store, d_info / h_info and the event
     hipEvent_t added = nullptr;
@@ -232,9 +234,35 @@ struct yv_ba_window {
     int solve_iters = 0, solve_nb = 0, solve_L = 0;
     double* solve_anchor = nullptr;
     WinFrames solve_F{};
+    // the multi-view mode (yv_ba_window_set_multiview): the records' query / train / parent and each frame's table
+    // train keypoint -> record in the store, the parentless records per frame on the host, the graph build's workspace
+    bool multiview = false, recorded = false;
+    int32_t *d_query = nullptr, *d_train = nullptr, *d_parent = nullptr, *d_tab = nullptr;
+    std::vector<int32_t> h_root;
+    yavo::WinTracks tracks{};
+    yavo::WinTracks solve_W{};
 };
 
 namespace {
+
+// the multi-view arrays of a store of `cap` frames, the first c0 frames copied over
+int win_reserve_links(yv_ba_window* w, int64_t cap, int64_t c0, hipStream_t st) {
+    const int64_t M = w->max_lm;
+    int32_t* a[4] = {nullptr, nullptr, nullptr, nullptr};
+    int32_t** old[4] = {&w->d_query, &w->d_train, &w->d_parent, &w->d_tab};
+    bool ok = true;
+    for (int i = 0; i < 4 && ok; ++i) ok = w->mem.alloc(&a[i], (size_t)(M * cap)) == YV_OK;
+    for (int i = 0; i < 4 && ok && c0 > 0 && *old[i]; ++i)
+        ok = hipMemcpyAsync(a[i], *old[i], sizeof(int32_t) * M * c0, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (ok && c0 > 0) ok = hipStreamSynchronize(st) == hipSuccess;
+    if (!ok) {
+        w->mem.release(a[0], a[1], a[2], a[3]);
+        return YV_ERR_HIP;
+    }
+    w->mem.release(w->d_query, w->d_train, w->d_parent, w->d_tab);
+    for (int i = 0; i < 4; ++i) *old[i] = a[i];
+    return YV_OK;
+}
 
 // the store covers frames [g0, end): grown by doubling, the recorded frames copied over (stream-ordered)
 int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
@@ -263,6 +291,7 @@ int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
              hipMemcpyAsync(edge, w->d_edge, sizeof(int32_t) * M * c0, hipMemcpyDeviceToDevice, st) == hipSuccess &&
              hipStreamSynchronize(st) == hipSuccess;
     }
+    if (ok && w->multiview) ok = win_reserve_links(w, cap, c0, st) == YV_OK;
     w->mem.release(w->d_T, w->d_X, w->d_uvo, w->d_uvp, w->d_cnt, w->d_edge);
     w->d_T = T;
     w->d_X = X;
@@ -272,6 +301,7 @@ int win_reserve(yv_ba_window* w, int64_t first, int64_t end, hipStream_t st) {
     w->d_edge = edge;
     w->cap = cap;
     w->h_cnt.resize((size_t)cap, -1);
+    w->h_root.resize((size_t)cap, 0);
     return ok ? YV_OK : YV_ERR_HIP;
 }
 
@@ -283,7 +313,10 @@ int win_collect(yv_ba_window* w) {
     const int64_t n = std::min<int64_t>(w->h_info[0], w->max_kf);
     for (int64_t j = 0; j < n; ++j) {
         const int64_t s = w->h_info[1 + 2 * j] - w->g0;
-        if (s >= 0 && s < w->cap) w->h_cnt[(size_t)s] = (int32_t)w->h_info[2 + 2 * j];
+        if (s >= 0 && s < w->cap) {
+            w->h_cnt[(size_t)s] = (int32_t)w->h_info[2 + 2 * j];
+            if (w->multiview) w->h_root[(size_t)s] = (int32_t)w->h_info[1 + 2 * (int64_t)w->max_kf + j];
+        }
     }
     return YV_OK;
 }
@@ -299,8 +332,8 @@ extern "C" int yv_ba_window_create(yv_ba* ba, int max_lm, int max_kf, yv_ba_wind
     w->ba = ba;
     w->max_lm = max_lm;
     w->max_kf = max_kf;
-    if (w->mem.alloc(&w->d_info, 1 + 2 * (size_t)max_kf) != YV_OK ||
-        w->mem.alloc_host(&w->h_info, 1 + 2 * (size_t)max_kf) != YV_OK ||
+    if (w->mem.alloc(&w->d_info, 1 + 3 * (size_t)max_kf) != YV_OK ||
+        w->mem.alloc_host(&w->h_info, 1 + 3 * (size_t)max_kf) != YV_OK ||
         w->mem.event(&w->added) != hipSuccess) {
         yv_ba_window_destroy(w);
         return YV_ERR_HIP;
@@ -333,12 +366,52 @@ extern "C" int yv_ba_window_reserve(yv_ba_window* w, int64_t n_frames) {
     return win_reserve(w, w->g0, w->g0 + n_frames, yavo::ctx_stream(w->ba->ctx));
 }
 
+extern "C" int yv_ba_window_set_multiview(yv_ba_window* w, int on) {
+    if (!w || w->solving) return YV_ERR_INVALID;
+    const bool want = on != 0;
+    if (want == w->multiview) return YV_OK;
+    if (w->recorded) return YV_ERR_INVALID;  // the recorded frames have no links (or links nothing would follow)
+    if (!want) {
+        w->multiview = false;
+        return YV_OK;
+    }
+    if (hipSetDevice(w->ba->dev) != hipSuccess) return YV_ERR_HIP;
+    yavo::WinTracks& t = w->tracks;
+    if (!t.up) {
+        const size_t nodes = (size_t)kWinMaxPoses * (size_t)w->max_lm, cls = (size_t)kWinMaxPoses * kWinMaxPoses;
+        if (w->mem.alloc(&t.up, nodes) != YV_OK || w->mem.alloc(&t.len, nodes) != YV_OK ||
+            w->mem.alloc(&t.rank, nodes) != YV_OK || w->mem.alloc(&t.lmk, nodes) != YV_OK ||
+            w->mem.alloc(&t.cnt, cls) != YV_OK || w->mem.alloc(&t.rp, cls) != YV_OK ||
+            w->mem.alloc(&t.lbase, cls) != YV_OK || w->mem.alloc(&t.ebase, cls) != YV_OK ||
+            w->mem.alloc(&t.rtot, (size_t)kWinMaxPoses) != YV_OK || w->mem.alloc(&t.A, cls + kWinMaxPoses) != YV_OK) {
+            w->mem.release(t.up, t.len, t.rank, t.lmk, t.cnt, t.rp, t.lbase, t.ebase, t.rtot, t.A);
+            return YV_ERR_HIP;
+        }
+        t.max_lm = w->max_lm;
+    }
+    // a store reserved before the switch gains its link arrays now (nothing is recorded in it yet)
+    if (w->cap > 0 && !w->d_query && win_reserve_links(w, w->cap, 0, yavo::ctx_stream(w->ba->ctx)) != YV_OK)
+        return YV_ERR_HIP;
+    w->multiview = true;
+    return YV_OK;
+}
+
 extern "C" int yv_ba_window_add_block(yv_ba_window* w, const void* d_block, int64_t first_frame, int n_frames,
                                       const double* d_edge_uv, const int32_t* d_edge_query, const void* d_matches,
                                       int max_kp, void* stream) {
+    return yv_ba_window_add_block_linked(w, d_block, first_frame, n_frames, d_edge_uv, d_edge_query, d_matches, max_kp,
+                                         nullptr, 0, stream);
+}
+
+extern "C" int yv_ba_window_add_block_linked(yv_ba_window* w, const void* d_block, int64_t first_frame, int n_frames,
+                                             const double* d_edge_uv, const int32_t* d_edge_query,
+                                             const void* d_matches, int max_kp, const int32_t* d_match_dj,
+                                             int64_t dj_stride, void* stream) {
     if (!w || !d_block || !d_edge_uv || !d_edge_query || !d_matches || n_frames < 1 || first_frame < 0 ||
         max_kp < 1 || max_kp > 65536 || w->solving)  // a pending solve reads the store: collect it first
         return YV_ERR_INVALID;
+    // multi-view: the links need the temporal pairs' match_dj, and every train keypoint a slot of the frame's table
+    if (w->multiview && (!d_match_dj || dj_stride < max_kp || max_kp > w->max_lm)) return YV_ERR_INVALID;
     if (hipSetDevice(w->ba->dev) != hipSuccess) return YV_ERR_HIP;
     hipStream_t st = stream ? reinterpret_cast<hipStream_t>(stream) : yavo::ctx_stream(w->ba->ctx);
     if (win_collect(w) != YV_OK) return YV_ERR_HIP;  // one block in flight: its info buffer is reused
@@ -348,9 +421,18 @@ extern "C" int yv_ba_window_add_block(yv_ba_window* w, const void* d_block, int6
                        d_edge_uv, d_edge_query, reinterpret_cast<const uint8_t*>(d_matches), max_kp, w->g0, w->cap,
                        w->max_lm,
                        w->d_T, w->d_cnt, w->d_edge, w->d_X, w->d_uvo, w->d_uvp, w->d_info);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpyAsync(w->h_info, w->d_info, sizeof(int64_t) * (1 + 2 * (size_t)w->max_kf), hipMemcpyDeviceToHost,
-                       st) != hipSuccess ||
+    if (hipGetLastError() != hipSuccess) return YV_ERR_HIP;
+    w->recorded = true;
+    if (w->multiview) {
+        const int64_t sc = first_frame - 1 - w->g0;
+        const int64_t carry = sc >= 0 && w->h_cnt[(size_t)sc] >= 0 ? first_frame - 1 : -1;
+        if (yavo::win_tracks_add(d_block, d_edge_query, d_match_dj, dj_stride, max_kp, carry, w->g0, w->cap, w->max_lm,
+                                 w->max_kf, w->d_query, w->d_train, w->d_tab, w->d_parent,
+                                 w->d_info + 1 + 2 * (int64_t)w->max_kf, st) != YV_OK)
+            return YV_ERR_HIP;
+    }
+    if (hipMemcpyAsync(w->h_info, w->d_info, sizeof(int64_t) * (1 + (w->multiview ? 3 : 2) * (size_t)w->max_kf),
+                       hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipEventRecord(w->added, st) != hipSuccess)
         return YV_ERR_HIP;
     w->add_pending = true;
@@ -386,8 +468,24 @@ extern "C" int yv_ba_window_solve_begin(yv_ba_window* w, int64_t first, int n, i
         w->solve_kind = 2;
         return YV_OK;
     }
-    const int E = 2 * L;
-    const int64_t nc = 3 * (int64_t)L;
+    // multi-view: the nodes are the L records counted above; a landmark per root -- every record of pose 1 (chains
+    // are cut at the window's start) and the parentless records after it -- and an edge per node and per root.  The
+    // co-visibility entries, sum (m + 1)(m + 2) / 2 over the chains, depend on the chains' lengths, which stay on the
+    // device: a node of pose i adds at most i + 1 (its chain starts at pose 0 at the earliest), a root one more
+    const bool mv = w->multiview;
+    const int N = L;
+    int64_t nc = 3 * (int64_t)L;
+    if (mv) {
+        L = F.c[1];
+        nc = 0;
+        for (int i = 1; i < n; ++i) {
+            if (i >= 2) L += std::min(w->h_root[(size_t)(F.s0 + i)], F.c[i]);
+            nc += (int64_t)F.c[i] * (i + 1);
+        }
+        nc += L;
+        if (nc > INT32_MAX) return YV_ERR_CAPACITY;
+    }
+    const int E = mv ? N + L : 2 * L;
     if (n > b->max_poses || L > b->max_landmarks || E > b->max_edges) return YV_ERR_CAPACITY;
     // per pose: its edges start (own edges of frame p, then the prev edges of frame p + 1); per row p1 of the
     // co-visibility buckets: (p1, p1) = c[p1] + c[p1 + 1] entries, (p1, p1 + 1) = c[p1 + 1]. win_build_kernel writes
@@ -404,16 +502,29 @@ extern "C" int yv_ba_window_solve_begin(yv_ba_window* w, int64_t first, int n, i
         if (hipStreamSynchronize(st) != hipSuccess) return YV_ERR_HIP;
         b->mem.release(b->d_cv_e1, b->d_cv_e2);
         b->cv_cap = 0;
-        if (b->mem.alloc(&b->d_cv_e1, nc) != YV_OK || b->mem.alloc(&b->d_cv_e2, nc) != YV_OK) return YV_ERR_HIP;
-        b->cv_cap = nc;
+        // multi-view: sized once for this window length with every slot of every frame taken, so that the frame loop
+        // allocates when the window grows to its full length and never after
+        const int64_t want = mv ? std::max<int64_t>(nc, (int64_t)w->max_lm * ((int64_t)n * (n + 1) / 2 + n)) : nc;
+        if (b->mem.alloc(&b->d_cv_e1, want) != YV_OK || b->mem.alloc(&b->d_cv_e2, want) != YV_OK) return YV_ERR_HIP;
+        b->cv_cap = want;
     }
     b->ready = false;
     yavo::BaParams& Q = b->P;
     const int nb = (std::max(L, n) + 255) / 256;
-    hipLaunchKernelGGL(win_build_kernel, dim3(nb), dim3(256), 0, st, F, L, w->max_lm, w->d_T, w->d_X, w->d_uvo,
-                       w->d_uvp, Q.poses, Q.X, b->d_ep, b->d_el, b->d_meas, b->d_le_off, b->d_le, b->d_pe, b->d_cv_e1,
-                       b->d_cv_e2, b->d_pe_off, b->d_cv_off);
-    if (hipGetLastError() != hipSuccess) return YV_ERR_HIP;
+    yavo::WinTracks W = w->tracks;
+    if (mv) {
+        W.P = n;
+        W.s0 = F.s0;
+        if (yavo::win_tracks_build(W, L, E, w->d_cnt, w->d_parent, w->d_T, w->d_X, w->d_uvo, w->d_uvp, Q.poses, Q.X,
+                                   b->d_ep, b->d_el, b->d_meas, b->d_le_off, b->d_le, b->d_pe_off, b->d_pe, b->d_cv_off,
+                                   b->d_cv_e1, b->d_cv_e2, st) != YV_OK)
+            return YV_ERR_HIP;
+    } else {
+        hipLaunchKernelGGL(win_build_kernel, dim3(nb), dim3(256), 0, st, F, L, w->max_lm, w->d_T, w->d_X, w->d_uvo,
+                           w->d_uvp, Q.poses, Q.X, b->d_ep, b->d_el, b->d_meas, b->d_le_off, b->d_le, b->d_pe,
+                           b->d_cv_e1, b->d_cv_e2, b->d_pe_off, b->d_cv_off);
+        if (hipGetLastError() != hipSuccess) return YV_ERR_HIP;
+    }
     Q.P = n;
     Q.nf = n_fixed;
     Q.np = n - n_fixed;
@@ -436,9 +547,15 @@ extern "C" int yv_ba_window_solve_begin(yv_ba_window* w, int64_t first, int n, i
     const int rc = ba_solve_enqueue(b, nullptr, nullptr, max_iters);
     if (rc != YV_OK) return rc;
     // the write-back in the same submission (skipped on the device if the solve suspends; _end reruns it then)
-    hipLaunchKernelGGL(win_scatter_kernel, dim3(nb), dim3(256), 0, st, F, L, w->max_lm, Q.poses, Q.X, w->d_T, w->d_X,
-                       d_anchor, static_cast<const int*>(&b->d_ctl->suspended));
-    if (hipGetLastError() != hipSuccess) return YV_ERR_HIP;
+    if (mv) {
+        if (yavo::win_tracks_scatter(W, w->d_cnt, Q.poses, Q.X, w->d_T, w->d_X, d_anchor,
+                                     static_cast<const int*>(&b->d_ctl->suspended), st) != YV_OK)
+            return YV_ERR_HIP;
+    } else {
+        hipLaunchKernelGGL(win_scatter_kernel, dim3(nb), dim3(256), 0, st, F, L, w->max_lm, Q.poses, Q.X, w->d_T,
+                           w->d_X, d_anchor, static_cast<const int*>(&b->d_ctl->suspended));
+        if (hipGetLastError() != hipSuccess) return YV_ERR_HIP;
+    }
     w->solving = true;
     w->solve_kind = 1;
     w->solve_iters = max_iters;
@@ -446,6 +563,7 @@ extern "C" int yv_ba_window_solve_begin(yv_ba_window* w, int64_t first, int n, i
     w->solve_L = L;
     w->solve_anchor = d_anchor;
     w->solve_F = F;
+    w->solve_W = W;
     return YV_OK;
 }
 
@@ -465,8 +583,15 @@ extern "C" int yv_ba_window_solve_end(yv_ba_window* w, double* chi2_log, int* it
     if (rc != YV_OK) return rc;
     if (b->resumed) {  // the write-back enqueued by _begin was skipped: the solve finished only now
         yavo::BaParams& Q = b->P;
-        hipLaunchKernelGGL(win_scatter_kernel, dim3(w->solve_nb), dim3(256), 0, st, w->solve_F, w->solve_L, w->max_lm,
-                           Q.poses, Q.X, w->d_T, w->d_X, w->solve_anchor, static_cast<const int*>(nullptr));
+        if (w->multiview) {
+            if (yavo::win_tracks_scatter(w->solve_W, w->d_cnt, Q.poses, Q.X, w->d_T, w->d_X, w->solve_anchor, nullptr,
+                                         st) != YV_OK)
+                return YV_ERR_HIP;
+        } else {
+            hipLaunchKernelGGL(win_scatter_kernel, dim3(w->solve_nb), dim3(256), 0, st, w->solve_F, w->solve_L,
+                               w->max_lm, Q.poses, Q.X, w->d_T, w->d_X, w->solve_anchor,
+                               static_cast<const int*>(nullptr));
+        }
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return YV_ERR_HIP;
     }
     if (iters) *iters = it;
@@ -499,6 +624,22 @@ extern "C" int yv_ba_window_read(yv_ba_window* w, int64_t frame, double* T_wc, i
         (X && k && hipMemcpy(X, w->d_X + 3 * o, sizeof(double) * 3 * k, hipMemcpyDeviceToHost) != hipSuccess) ||
         (uv_own && k && hipMemcpy(uv_own, w->d_uvo + 2 * o, sizeof(double) * 2 * k, hipMemcpyDeviceToHost) != hipSuccess) ||
         (uv_prev && k && hipMemcpy(uv_prev, w->d_uvp + 2 * o, sizeof(double) * 2 * k, hipMemcpyDeviceToHost) != hipSuccess))
+        return YV_ERR_HIP;
+    return YV_OK;
+}
+
+extern "C" int yv_ba_window_read_links(yv_ba_window* w, int64_t frame, int32_t* query, int32_t* train,
+                                       int32_t* parent, int cap) {
+    if (!w || w->solving || !w->multiview || cap < 0) return YV_ERR_INVALID;
+    if (hipSetDevice(w->ba->dev) != hipSuccess || win_collect(w) != YV_OK) return YV_ERR_HIP;
+    const int64_t s = frame - w->g0;
+    if (w->g0 < 0 || s < 0 || s >= w->cap || w->h_cnt[(size_t)s] < 0) return YV_ERR_INVALID;
+    if (hipStreamSynchronize(yavo::ctx_stream(w->ba->ctx)) != hipSuccess) return YV_ERR_HIP;
+    const int k = std::min(w->h_cnt[(size_t)s], cap);
+    const int64_t o = s * w->max_lm;
+    if ((query && k && hipMemcpy(query, w->d_query + o, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (train && k && hipMemcpy(train, w->d_train + o, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (parent && k && hipMemcpy(parent, w->d_parent + o, sizeof(int32_t) * k, hipMemcpyDeviceToHost) != hipSuccess))
         return YV_ERR_HIP;
     return YV_OK;
 }

@@ -537,4 +537,29 @@ int ba_ensure_schur(yv_ba* b, int np, hipStream_t st);
 int ba_solve_enqueue(yv_ba* b, const double* poses, const double* landmarks, int max_iters);
 int ba_solve_wait(yv_ba* b, double* poses, double* landmarks, int max_iters, double* chi2_log, int* iters);
 
+// ---- the window's multi-view mode (yavo_ba_window_tracks.hip), as yavo_ba_window.hip drives it ----
+// One window's nodes and tables: node (i, l) = record l of window pose i >= 1, id = i * max_lm + l.
+struct WinTracks {
+    int P = 0;        // window poses
+    int max_lm = 0;
+    int64_t s0 = 0;   // store index of the window's first frame
+    int32_t *up = nullptr, *len = nullptr, *rank = nullptr, *lmk = nullptr;  // [kWinMaxPoses * max_lm] per node:
+                                                                             // root id; at roots the chain length
+                                                                             // and the rank in its class; landmark
+    int32_t *cnt = nullptr, *rp = nullptr, *lbase = nullptr, *ebase = nullptr;  // [P][P] per class (s, e)
+    int32_t *rtot = nullptr, *A = nullptr;                                      // [P], [P + 1][P]
+};
+// the records win_add_kernel just wrote gain query / train / parent and their frame its train -> record table;
+// d_roots[j] = records of keyframe j without a parent.  carry_frame: first_frame - 1 where recorded, else -1
+int win_tracks_add(const void* d_block, const int32_t* d_edge_query, const int32_t* d_match_dj, int64_t dj_stride,
+                   int max_kp, int64_t carry_frame, int64_t g0, int64_t cap, int max_lm, int max_kf, int32_t* d_query,
+                   int32_t* d_train, int32_t* d_tab, int32_t* d_parent, int64_t* d_roots, hipStream_t st);
+// the multi-view graph of the window (L landmarks, E edges, as the host counted them) into the yv_ba's arrays
+int win_tracks_build(const WinTracks& W, int L, int E, const int32_t* d_cnt, const int32_t* d_parent, const double* d_T,
+                     const double* d_Xs, const double* d_uvo, const double* d_uvp, double* poses, double* X,
+                     int32_t* ep, int32_t* el, double* meas, int32_t* le_off, int32_t* le, int32_t* pe_off, int32_t* pe,
+                     int32_t* cv_off, int32_t* cv1, int32_t* cv2, hipStream_t st);
+int win_tracks_scatter(const WinTracks& W, const int32_t* d_cnt, const double* poses, const double* X, double* d_T,
+                       double* d_Xs, double* d_anchor, const int* gate, hipStream_t st);
+
 }  // namespace yavo

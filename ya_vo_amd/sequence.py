@@ -10,6 +10,8 @@ Optimizer, first 200 frames"), driven the way LoopHandler drives its loop (src/L
   (held fixed: they were refined with the previous chunk and pin the gauge and the scale): every landmark of frame k
   (its pose-LM inliers, X_w from the map) observed in frame k (its left keypoint) and frame k-1 (the PnP
   measurement); the refined poses replace the trajectory's and the last one anchors the next chunk.
+  multiview=True (opt-in): the landmarks the temporal matches follow from frame to frame enter the window once,
+  observed by every frame of their chain (window_problem_tracks states the rule).
 
 Host logic only (the window assembly and SE3 inversion are numpy); every compute step is a libyavo kernel.
 tests/sequence_chain.py restates the same loop over the CPU oracle for the trajectory check.
@@ -50,13 +52,17 @@ class FrameRecord:
     X: np.ndarray = field(default_factory=lambda: np.zeros((0, 3)))
     uv_prev: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))  # in frame k-1 (the PnP measurement)
     uv_own: np.ndarray = field(default_factory=lambda: np.zeros((0, 2)))   # in frame k (its left keypoint)
+    # multi-view linking (window_problem_tracks): the keypoint indices of the temporal match behind each landmark
+    query: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))  # in L_{k-1}
+    train: np.ndarray = field(default_factory=lambda: np.zeros(0, np.int64))  # in L_k
 
 
 def frame_records_from_block(block: np.ndarray, edge_uv: np.ndarray, edge_query: np.ndarray,
-                             own_px: np.ndarray) -> Dict[int, FrameRecord]:
+                             own_px: np.ndarray, match_dj: np.ndarray = None) -> Dict[int, FrameRecord]:
     """Placed map block + the chunk's edge arrays -> per-frame records. edge_uv [n, max_kp, 2] and edge_query
     [n, max_kp] per track (track k = frame first_frame + k); own_px [n, max_kp, 2] = the frame-k keypoint the
-    query's temporal match selected (Matches::pt2, row / col)."""
+    query's temporal match selected (Matches::pt2, row / col). match_dj [n, max_kp, 2] (the temporal pairs'
+    {distance, train index} per query), when given, fills the records' query / train indices."""
     h, kfs, lms = ymap.parse_block(block)
     first = int(h["first_frame"])
     out = {}
@@ -67,6 +73,9 @@ def frame_records_from_block(block: np.ndarray, edge_uv: np.ndarray, edge_query:
         q = edge_query[k, e]
         out[g] = FrameRecord(np.array(kf["T"], np.float64), e, np.array(lm["X"], np.float64),
                              edge_uv[k, e].astype(np.float64), own_px[k, q].astype(np.float64))
+        if match_dj is not None:
+            out[g].query = q.astype(np.int64)
+            out[g].train = match_dj[k, q, 1].astype(np.int64)
     return out
 
 
@@ -108,6 +117,70 @@ def apply_window(records: Dict[int, FrameRecord], frames: List[int], poses: np.n
             base += n
 
 
+def window_problem_tracks(records: Dict[int, FrameRecord], frames: List[int], n_fixed: int):
+    """The multi-view BA problem over consecutive `frames` (oldest first). The nodes are window_problem's landmarks:
+    the records (i, l) of pose index i = 1 .. P-1. The parent of (i, l), i >= 2, is the smallest l' with
+    train[i-1][l'] == query[i][l] (the temporal match of frame i starts at the keypoint the match of frame i-1 ended
+    on); without one, and at pose 1 (chains are cut at the window's start), the node is a root. Queries of one record
+    list are distinct, so chains are simple paths; of two records sharing a train keypoint the later stays alone.
+    A chain with its root at pose a and m nodes is one landmark with m + 1 edges in pose order -- (a-1, root uv_prev),
+    (a, root uv_own), (a+1, child uv_own), ... -- and the root's X. Landmarks ascend by (a, m, root's l); edges are
+    landmark-major. -> (poses, X, ep, el, meas, node_map), node_map[i][l] = the landmark of record (i, l)."""
+    P = len(frames)
+    poses = np.stack([se3_inverse(records[g].T_wc) for g in frames])
+    recs = [records[g] for g in frames]
+    chains: List[List[Tuple[int, int]]] = []   # per root, its nodes in pose order
+    chain_of: List[np.ndarray] = [np.zeros(0, np.int64)]
+    for i in range(1, P):
+        r = recs[i]
+        n = len(r.edge)
+        mine = np.zeros(n, np.int64)
+        first: Dict[int, int] = {}
+        if i >= 2:
+            if len(r.query) != n or len(recs[i - 1].train) != len(recs[i - 1].edge):
+                raise ValueError("records without query / train indices (frame_records_from_block needs match_dj)")
+            for lp in range(len(recs[i - 1].train) - 1, -1, -1):
+                first[int(recs[i - 1].train[lp])] = lp
+        for l in range(n):
+            lp = first.get(int(r.query[l]), -1) if i >= 2 else -1
+            if lp < 0:
+                mine[l] = len(chains)
+                chains.append([(i, l)])
+            else:
+                mine[l] = chain_of[i - 1][lp]
+                chains[mine[l]].append((i, l))
+        chain_of.append(mine)
+    order = sorted(range(len(chains)), key=lambda c: (chains[c][0][0], len(chains[c]), chains[c][0][1]))
+    lm_of = np.zeros(len(chains), np.int64)
+    Xs, ep, el, meas = [], [], [], []
+    for lm, c in enumerate(order):
+        lm_of[c] = lm
+        a, l0 = chains[c][0]
+        Xs.append(recs[a].X[l0])
+        ep.append(a - 1)
+        meas.append(recs[a].uv_prev[l0])
+        for i, l in chains[c]:
+            ep.append(i)
+            meas.append(recs[i].uv_own[l])
+        el += [lm] * (len(chains[c]) + 1)
+    node_map = [lm_of[m] if len(m) else m for m in chain_of]
+    if not Xs:
+        return poses, np.zeros((0, 3)), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros((0, 2)), node_map
+    return (poses, np.array(Xs, np.float64).reshape(-1, 3), np.array(ep, np.int32), np.array(el, np.int32),
+            np.array(meas, np.float64).reshape(-1, 2), node_map)
+
+
+def apply_window_tracks(records: Dict[int, FrameRecord], frames: List[int], poses: np.ndarray, X: np.ndarray,
+                        node_map) -> None:
+    """Write a solved multi-view window back: T_wc = inverse(T_cw) per frame; every node of a chain takes its
+    landmark's refined X."""
+    for g, T in zip(frames, poses):
+        records[g].T_wc = se3_inverse(T)
+    for g, m in zip(frames, node_map):
+        if len(m):
+            records[g].X = X[m].copy()
+
+
 # poses of one device BA window (yv_ba_window_solve, yavo_ba_window.hip kWinMaxPoses)
 WINDOW_MAX_POSES = 128
 
@@ -117,13 +190,15 @@ class SequenceFrontend:
 
     def __init__(self, ctx, chunk: int, K, T_right, n_fixed: int = 2, ba_iters: int = 10,
                  H: int = 376, W: int = 1241, max_kp: int = 2000, match_thr: int = 20, device_window: bool = True,
-                 ba_priority: int = 0, expected_frames: int = 0, ba_stream=None):
+                 ba_priority: int = 0, expected_frames: int = 0, ba_stream=None, multiview: bool = False):
         """device_window: the BA window is recorded, assembled and written back on the device (yv_ba_window_*,
         no per-chunk read-back); False: the host assembly below (window_problem / apply_window), kept as the
         restatement the device path is checked against. ba_priority: the BA stream's priority (torch's convention:
         -1 high, 0 default) against the context stream the next chunk's kernels run on. expected_frames: the
         sequence length when known (the device window's record store is sized for it up front instead of growing by
-        doubling, which synchronises the device inside the loop)."""
+        doubling, which synchronises the device inside the loop). multiview: landmarks the temporal matches follow over
+        several frames enter the window once, observed by every frame of their chain (window_problem_tracks; on the
+        device yv_ba_window_set_multiview), instead of once per frame with two observations."""
         import torch
         from . import Batch, BaWindow, BundleAdjuster
         if chunk < 2 or n_fixed < 1:
@@ -158,6 +233,8 @@ class SequenceFrontend:
         self._h_uv = pinned(chunk * max_kp * 16)
         self._h_q = pinned(chunk * max_kp * 4)
         self._h_m = pinned(2 * chunk * max_kp * 100)
+        self.multiview = bool(multiview)
+        self._h_dj = pinned(2 * chunk * max_kp * 8) if multiview and not device_window else None
         self.ba = BundleAdjuster(ctx, window, window * max_kp, 2 * window * max_kp)
         # the BA beside the next chunk's kernels: by default the context's side stream, whose hardware queue is never
         # the context stream's (a fresh torch stream shares it one time in four and the two serialise: yv_side_stream);
@@ -169,6 +246,8 @@ class SequenceFrontend:
         self._ba_pending = False
         self.device_window = device_window
         self.win = BaWindow(self.ba, max_kp, chunk) if device_window else None
+        if self.win is not None and multiview:
+            self.win.set_multiview(True)
         if self.win is not None and expected_frames > 0:
             self.win.reserve(expected_frames)
         self._records: Dict[int, FrameRecord] = {}
@@ -224,7 +303,10 @@ class SequenceFrontend:
         q = ctx.download(v.edge_query, np.int32, n * kp, out=self._h_q).reshape(n, kp)
         m = ctx.download(v.matches, np.uint8, 2 * n * kp * 100, out=self._h_m).reshape(2 * n, kp, 100)[0::2]
         own = m[:, :, 48:56].copy().view(np.int32).reshape(n, kp, 2)  # Matches::pt2.{x, y}
-        self._records.update(frame_records_from_block(block, uv, q, own))
+        dj = None
+        if self.multiview:
+            dj = ctx.download(v.match_dj, np.int32, 2 * n * kp * 2, out=self._h_dj).reshape(2 * n, kp, 2)[0::2]
+        self._records.update(frame_records_from_block(block, uv, q, own, dj))
         self.next_frame = first + n
         self._ba_pending = True
         t4 = time.perf_counter()
@@ -246,7 +328,8 @@ class SequenceFrontend:
         t2 = time.perf_counter()
         ctx.map_place(self.d_block.data_ptr(), 1, self.bb, self.d_base.data_ptr(), self.d_anchors.data_ptr())
         v = self.batch.view()
-        self.win.add_block(self.d_block.data_ptr(), first, n, v.edge_uv, v.edge_query, v.matches, self.max_kp)
+        self.win.add_block(self.d_block.data_ptr(), first, n, v.edge_uv, v.edge_query, v.matches, self.max_kp,
+                           d_match_dj=v.match_dj if self.multiview else 0)
         self.next_frame = first + n
         t3 = time.perf_counter()
         self._local_ba_device_begin()
@@ -293,7 +376,9 @@ class SequenceFrontend:
         if len(frames) <= self.n_fixed:
             return
         t0 = time.perf_counter()
-        poses, X, ep, el, meas, owners = window_problem(self._records, frames, self.n_fixed)
+        assemble, apply = (window_problem_tracks, apply_window_tracks) if self.multiview else \
+            (window_problem, apply_window)
+        poses, X, ep, el, meas, owners = assemble(self._records, frames, self.n_fixed)
         if len(ep) == 0:
             return
         t1 = time.perf_counter()
@@ -301,7 +386,7 @@ class SequenceFrontend:
         t2 = time.perf_counter()
         poses, X, log, it = self.ba.solve(poses, X, self.ba_iters)
         t3 = time.perf_counter()
-        apply_window(self._records, frames, poses, X, owners)
+        apply(self._records, frames, poses, X, owners)
         sec["ba_assemble"] = t1 - t0 + time.perf_counter() - t3
         sec["ba_set_problem"] = t2 - t1
         sec["ba_solve"] = t3 - t2
@@ -339,8 +424,11 @@ class SequenceShard:
     frames gives, bit for bit; the BA windows do not straddle shards (replicas)."""
 
     def __init__(self, ctx, rank: int, world: int, frames_per_rank: int, chunk: int, K, T_right, n_fixed: int = 2,
-                 ba_iters: int = 10, H: int = 376, W: int = 1241, max_kp: int = 2000, match_thr: int = 20):
+                 ba_iters: int = 10, H: int = 376, W: int = 1241, max_kp: int = 2000, match_thr: int = 20,
+                 multiview: bool = False):
         import torch
+        if multiview:
+            raise ValueError("SequenceShard runs two-view windows only (no sharded placement of merged landmarks)")
         if frames_per_rank % chunk:
             raise ValueError("frames_per_rank must be a multiple of chunk")
         self.ctx, self.rank, self.world, self.n, self.max_kp = ctx, rank, world, frames_per_rank, max_kp
