@@ -288,6 +288,61 @@ typedef struct yv_batch_subpix_view {
 } yv_batch_subpix_view;
 /* Device views of the refinement's arrays (the last run with it on); YV_ERR_INVALID before it was ever switched on. */
 int yv_batch_subpix_view_get(yv_batch* b, yv_batch_subpix_view* v);
+/* ---- scale pyramid: multi-scale keypoints merged into the batch's slots (beyond the reference; exact, all integer) ---- */
+/* n_levels in 2..8 levels of sizes level_hw[2 * l ..] = (H_l, W_l): level 0 is the batch's H x W, the sizes do not grow
+ * and shrink by at most 2 per level (2 H_l >= H_(l-1), 2 W_l >= W_(l-1)), and every size is one yv_batch_create accepts.
+ * Level l is the integer bilinear resample of level l - 1, centre-aligned: the source position of destination row r, in
+ * 1/32 pixel, is qv = clamp(floor(((2 r + 1) H_(l-1) - H_l) * 16 / H_l), 0, (H_(l-1) - 1) * 32), of column c the same
+ * with W; the pixel is yv_rectify_image's four-tap blend at (qu, qv) (yavo_io.h), whose taps all lie inside the source.
+ * Every level runs detect, the context's keypoint selection, the cut at min(level_keep[l], max_corners) and BRIEF
+ * (steered when the context's steering is on) on its own image and its own blur, exactly as yv_detect + yv_describe
+ * with max_kp = level_keep[l] do on that image.  The keypoints of levels 1 .. L - 1 are then appended to their image's
+ * slot behind level 0's, in level order and inside a level in that level's keypoint order: featVec and the internal
+ * descriptor copied, matched = 0, id = the index in the merged list, x = floor((2 x_l + 1) H_0 / (2 H_l)), y the same
+ * with W; with steering the bin and the moments travel with the record.  kp_count becomes the merged count; det_count,
+ * det_rc, det_resp and cand_count of yv_batch_view stay level 0's.  From the match stage on a run works on the merged
+ * slots unchanged.  n_levels <= 1 switches the pyramid off (the default; the arrays are then ignored) and yv_batch_run
+ * launches exactly what it launched before.  In yv_batch_stage_times the level images and the levels' detect count in
+ * stage 0, their selection and cut in stage 1, their BRIEF and the merge in stage 2.  The level workspaces are allocated by the first call that switches it on
+ * and kept while the sizes stay the same; a call that switches it on waits for the device.
+ * Checked in this order, before the batch is looked at where the batch is not needed: YV_ERR_INVALID for a NULL array
+ * with n_levels > 1, n_levels > 8, a side below 9, a negative quota, a level 0 that differs from the batch, a level
+ * larger than the one before it or less than half of it; YV_ERR_CAPACITY for a sum of the quotas above max_kp or a
+ * level with W > 2048 or H > 8192; then YV_ERR_INVALID for a NULL batch. */
+#define YV_PYRAMID_MAX_LEVELS 8
+int yv_batch_set_pyramid(yv_batch* b, int n_levels, const int32_t* level_hw /* [n_levels][2] */,
+                         const int32_t* level_keep /* [n_levels] */);
+typedef struct yv_batch_pyramid_view {
+    int n_levels;
+    int H[YV_PYRAMID_MAX_LEVELS], W[YV_PYRAMID_MAX_LEVELS], keep[YV_PYRAMID_MAX_LEVELS];
+    /* level l's images: image i at image[l] + i * pitch[l], rows stride[l] bytes apart (level 0: NULL, the run's own) */
+    const uint8_t* image[YV_PYRAMID_MAX_LEVELS];
+    int stride[YV_PYRAMID_MAX_LEVELS];
+    int64_t pitch[YV_PYRAMID_MAX_LEVELS];
+    const int32_t* kp_count[YV_PYRAMID_MAX_LEVELS];    /* [max_images + 1] the level's keypoints per image */
+    const int32_t* det_count[YV_PYRAMID_MAX_LEVELS];   /* [max_images + 1] the level's corners after its cut */
+    /* [max_images + 1][max_kp] the level's own records (level 0: the head of the merged slot) */
+    const yv_keypoint* keypoints[YV_PYRAMID_MAX_LEVELS];
+    const uint8_t* level;             /* [max_images + 1][max_kp] the level of every merged keypoint */
+    const int32_t* level_rc;          /* [max_images + 1][max_kp][2] its (row, col) on its own level */
+} yv_batch_pyramid_view;
+/* Device views of the last run with the pyramid on; the carry slot's level / level_rc rows (and kp_count[0]) are copied
+ * with its keypoints.  YV_ERR_INVALID before the pyramid was ever switched on. */
+int yv_batch_pyramid_view_get(yv_batch* b, yv_batch_pyramid_view* v);
+/* The host-pointer form for one image: the merged list of a one-image batch with max_kp = the sum of the quotas
+ * (at most 4096) into out / level / level_rc (capacity: that sum), *n_out = the merged count.  n_levels = 1 is the
+ * single-scale detect + describe with the cut at level_keep[0].  The argument checks of yv_batch_set_pyramid with the
+ * image's H x W as the batch's, and YV_ERR_INVALID for a NULL img or n_out, n_levels < 1, H < 9, W < 9 or stride < W,
+ * all before the context; then, as in yv_match_knn2, YV_ERR_NODEVICE for a NULL context on a machine without a GPU. */
+int yv_detect_describe_pyramid(yv_ctx* ctx, const uint8_t* img, int H, int W, int stride, int n_levels,
+                               const int32_t* level_hw, const int32_t* level_keep, yv_keypoint* out, uint8_t* level,
+                               int32_t* level_rc /* [n][2] */, int* n_out);
+/* One level step on host pointers: dst (dst_H x dst_W, rows dst_stride bytes apart; the bytes between the rows stay
+ * the caller's) = the resample above of src.  YV_ERR_INVALID for a NULL src or dst, a size outside
+ * 1 <= dst <= src <= min(2 dst, 8192) per axis or a stride below its width, checked before the context. */
+int yv_pyramid_image(yv_ctx* ctx, const uint8_t* src, int src_H, int src_W, int src_stride, int dst_H, int dst_W,
+                     uint8_t* dst, int dst_stride);
+
 /* Tracking (PnP) over the last run's matches: track t = {stereo_pair, temporal_pair} (pair indices of
  * yv_batch_set_pairs) where the stereo pair's query image (frame k left) is the temporal pair's train
  * image.  Each frame-(k-1) keypoint kept by removeOutliers in the temporal pair whose frame-k keypoint is

@@ -74,6 +74,13 @@ class _BatchSubpixView(ctypes.Structure):
     _fields_ = [("dcol_q8", ctypes.c_void_p), ("sad", ctypes.c_void_p), ("status", ctypes.c_void_p)]
 
 
+class _BatchPyramidView(ctypes.Structure):
+    _fields_ = [("n_levels", ctypes.c_int), ("H", ctypes.c_int * 8), ("W", ctypes.c_int * 8),
+                ("keep", ctypes.c_int * 8), ("image", ctypes.c_void_p * 8), ("stride", ctypes.c_int * 8),
+                ("pitch", ctypes.c_int64 * 8), ("kp_count", ctypes.c_void_p * 8), ("det_count", ctypes.c_void_p * 8),
+                ("keypoints", ctypes.c_void_p * 8), ("level", ctypes.c_void_p), ("level_rc", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # symbol -> (restype, argtypes); the same list the C header declares (tests check they all resolve)
@@ -116,6 +123,10 @@ SIGNATURES = {
     "yv_stereo_subpix": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "yv_batch_set_stereo_subpix": (_I, [_P, _P, _I, _I, _I, _I]),
     "yv_batch_subpix_view_get": (_I, [_P, ctypes.POINTER(_BatchSubpixView)]),
+    "yv_batch_set_pyramid": (_I, [_P, _I, _P, _P]),
+    "yv_batch_pyramid_view_get": (_I, [_P, ctypes.POINTER(_BatchPyramidView)]),
+    "yv_detect_describe_pyramid": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.POINTER(_I)]),
+    "yv_pyramid_image": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _I]),
     "yv_batch_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_batch_destroy": (None, [_P]),
     "yv_batch_set_pairs": (_I, [_P, _P, _I]),
@@ -575,6 +586,36 @@ class Context(_GeomMixin):
                "yv_describe")
         return out[:m.value].copy()
 
+    def detect_describe_pyramid(self, img: np.ndarray, sizes, quotas):
+        """yv_detect_describe_pyramid: the merged multi-scale keypoints of one image over the levels sizes [L][2] =
+        (H_l, W_l) (ya_vo_amd.pyramid.level_sizes) with the quotas [L] -> (KEYPOINT_DTYPE array, level [n] uint8,
+        level_rc [n, 2] int32)."""
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        H, W = img.shape
+        hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+        keep = np.ascontiguousarray(np.asarray(quotas, dtype=np.int32).reshape(-1))
+        if len(hw) != len(keep):
+            raise ValueError("one quota per level")
+        cap = max(int(keep.clip(0).sum()), 1)
+        out = np.zeros(cap, KEYPOINT_DTYPE)
+        level = np.zeros(cap, np.uint8)
+        rc = np.zeros((cap, 2), np.int32)
+        n = ctypes.c_int()
+        _check(self.lib.yv_detect_describe_pyramid(self.handle, _ptr(img), H, W, W, len(hw), _ptr(hw), _ptr(keep),
+                                                   _ptr(out), _ptr(level), _ptr(rc), ctypes.byref(n)),
+               "yv_detect_describe_pyramid")
+        return out[:n.value].copy(), level[:n.value].copy(), rc[:n.value].copy()
+
+    def pyramid_image(self, src: np.ndarray, dst_H: int, dst_W: int) -> np.ndarray:
+        """yv_pyramid_image: one level step, the integer bilinear resample of src to dst_H x dst_W."""
+        if src.dtype != np.uint8 or src.ndim != 2 or src.strides[1] != 1:
+            src = np.ascontiguousarray(src, dtype=np.uint8)
+        H, W = src.shape
+        dst = np.zeros((dst_H, dst_W), np.uint8)
+        _check(self.lib.yv_pyramid_image(self.handle, ctypes.c_void_p(src.ctypes.data), H, W, src.strides[0], dst_H,
+                                         dst_W, _ptr(dst), dst_W), "yv_pyramid_image")
+        return dst
+
     def match_features(self, q: np.ndarray, t: np.ndarray) -> np.ndarray:
         """Brief::matchFeatures -> MATCH_DTYPE array (one per query)."""
         q = np.ascontiguousarray(q, dtype=KEYPOINT_DTYPE)
@@ -807,6 +848,27 @@ class Batch:
         on): dcol_q8 and sad [max_pairs][max_kp] int32, status [max_pairs][max_kp] uint8, by query keypoint."""
         v = _BatchSubpixView()
         _check(self.lib.yv_batch_subpix_view_get(self.handle, ctypes.byref(v)), "yv_batch_subpix_view_get")
+        return v
+
+    def set_pyramid(self, sizes=None, quotas=None) -> None:
+        """The scale pyramid of the following runs (yv_batch_set_pyramid): sizes [L][2] = (H_l, W_l) with level 0 the
+        batch's size (ya_vo_amd.pyramid.level_sizes) and one keypoint quota per level (level_quotas); None (the
+        default) or a single level switches it off."""
+        if sizes is None or len(sizes) <= 1:
+            _check(self.lib.yv_batch_set_pyramid(self.handle, 0, None, None), "yv_batch_set_pyramid")
+            return
+        hw = np.ascontiguousarray(np.asarray(sizes, dtype=np.int32).reshape(-1, 2))
+        keep = np.ascontiguousarray(np.asarray(quotas, dtype=np.int32).reshape(-1))
+        if len(hw) != len(keep):
+            raise ValueError("one quota per level")
+        _check(self.lib.yv_batch_set_pyramid(self.handle, len(hw), _ptr(hw), _ptr(keep)), "yv_batch_set_pyramid")
+
+    def pyramid_view(self) -> _BatchPyramidView:
+        """Device arrays of the pyramid (yv_batch_pyramid_view_get; after set_pyramid switched it on): per level the
+        images, kp_count / det_count [max_images + 1] int32 and the level's own keypoints; level [max_images + 1]
+        [max_kp] uint8 and level_rc [max_images + 1][max_kp][2] int32 of the merged keypoints."""
+        v = _BatchPyramidView()
+        _check(self.lib.yv_batch_pyramid_view_get(self.handle, ctypes.byref(v)), "yv_batch_pyramid_view_get")
         return v
 
     def orient_view(self) -> _BatchOrientView:

@@ -85,6 +85,7 @@ void batch_free(yv_batch* b) {
     if (b->side) (void)hipStreamSynchronize(b->side);
     if (b->rstream) (void)hipStreamSynchronize(b->rstream);  // (the owner destroys streams before it frees memory)
     if (b->lk) yv_lk_destroy(b->lk);
+    pyramid_free(b);
     delete b;
 }
 
@@ -534,11 +535,16 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
     hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
     const int H = b->H, W = b->W, K = b->max_kp;
-    const int keep = std::min(ctx->max_corners, K);
+    const bool pyr = b->pyr_on;  // levels -> per-level stages -> merge in place of stages 0-2 (yv_batch_set_pyramid)
+    const int keep = std::min(ctx->max_corners, pyr ? b->pyr[0].keep : K);
     const int sel = prepare_select(b, H, W);
     if (sel != YV_OK) return sel;
     const bool steer = steer_on(ctx);
     if (steer && ensure_steer(b) != YV_OK) return YV_ERR_HIP;
+    if (pyr) {
+        const int pp = pyramid_prepare(b);
+        if (pp != YV_OK) return pp;
+    }
     const bool defer_records = b->rstream && b->n_tracks > 0 && b->timing != 1;  // (with copy_counts below)
     if (defer_records && ensure_match_pos(b) != YV_OK) return YV_ERR_HIP;
     if (b->pending_carry >= 0 && (join_build(b, s) != YV_OK || join_records(b, s) != YV_OK)) return YV_ERR_HIP;
@@ -553,6 +559,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
             YV_HIP(hipMemcpyAsync(b->steer_mom + dst * nk * 2, b->steer_mom + c * nk * 2, nk * 2 * sizeof(int32_t),
                                   hipMemcpyDeviceToDevice, s));
         }
+        if (pyr && pyramid_carry(b, c, s) != YV_OK) return YV_ERR_HIP;  // and their levels
         b->pending_carry = -1;
     }
     int run = -1;
@@ -562,9 +569,11 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     rc |= record_stage(b, s, run, 0);
     yavo::launch_detect_blur(d_images, n_images, H, W, stride, image_pitch, ctx->fast_thr, ctx->harris_eigen, b->cand_keys, b->cap,
                              b->cand_count, ctx->k9, b->blur, s);
+    if (pyr) pyramid_detect(b, d_images, n_images, stride, image_pitch, s);
     rc |= record_stage(b, s, run, 1);
     if (b->overlap_mode == 2) rc |= launch_deferred_after(b, s);
     launch_select_topk(b, n_images, keep, s);
+    if (pyr) pyramid_topk(b, n_images, s);
     rc |= record_stage(b, s, run, 2);
     if (b->overlap_mode == 4) rc |= launch_deferred_after(b, s);  // after top-K
     // the previous track's build (beside detect and top-K) reads keypoints / matches: BRIEF and finalize rewrite them
@@ -572,6 +581,7 @@ int yv_batch_run(yv_batch* b, const uint8_t* d_images, int n_images, int stride,
     rc |= join_build(b, s);
     rc |= join_records(b, s);  // and the previous run's deferred match records read keypoints
     launch_describe(b, n_images, brief_workers(ctx, W), s);
+    if (pyr) pyramid_describe_merge(b, n_images, s);
     rc |= record_stage(b, s, run, 3);
     if (b->overlap_mode == 3) rc |= launch_deferred_after(b, s);  // after describe
     b->run_flags = b->n_pairs > 0 ? b->match_flags : 0;

@@ -268,6 +268,19 @@ struct yv_batch {
     int32_t* subpix_dcol = nullptr;   // [max_pairs][max_kp] dcol_q8, by query keypoint
     int32_t* subpix_sad = nullptr;    // [max_pairs][max_kp]
     uint8_t* subpix_status = nullptr; // [max_pairs][max_kp]
+    // the scale pyramid (yv_batch_set_pyramid): the sidecar is allocated by the first call that switches it on, a
+    // level's workspace (a batch of that level's size, which owns the level's images) while the sizes stay the same
+    struct PyrLevel {
+        int H = 0, W = 0, keep = 0, stride = 0;
+        uint8_t* img = nullptr;     // [max_images][H][stride] (level 0: the run's images)
+        yv_batch* ws = nullptr;     // levels >= 1
+    };
+    bool pyr_on = false;
+    int pyr_levels = 0;
+    PyrLevel pyr[8];
+    uint8_t* pyr_level = nullptr;   // [slot][max_kp] the level of every merged keypoint
+    int32_t* pyr_rc = nullptr;      // [slot][max_kp][2] its position on its own level
+    int32_t* pyr_count0 = nullptr;  // [slot] level 0's keypoints
     uint8_t* staging = nullptr;  // one H x W input image (host-pointer API)
     std::vector<int32_t> h_pairs;   // host copy of the pairs (track validation)
     // tracks (PnP over the matches)
@@ -470,6 +483,16 @@ int prepare_select(yv_batch* b, int H, int W);
 void launch_select_topk(yv_batch* b, int n_images, int keep, hipStream_t s);
 void launch_describe(yv_batch* b, int n_images, int max_workers, hipStream_t s);
 int match_stage(yv_batch* b, MatchStage st, hipStream_t s, int run);
+
+// ---- the scale pyramid (yavo_pyramid.hip), as yv_batch_run drives it: the levels >= 1 of a run with the pyramid on ----
+void pyramid_free(yv_batch* b);   // the level workspaces (batch_free's part)
+int pyramid_prepare(yv_batch* b);  // the levels' selection preflight and steering arrays, before any copy or launch
+int pyramid_carry(yv_batch* b, size_t from, hipStream_t s);  // slot `from`'s sidecar into the carry slot
+// stage 0: level images and the levels' detect; stage 1: their selection and cut; stage 2: their BRIEF and the merge
+void pyramid_detect(yv_batch* b, const uint8_t* d_images, int n_images, int stride, int64_t image_pitch,
+                    hipStream_t s);
+void pyramid_topk(yv_batch* b, int n_images, hipStream_t s);
+void pyramid_describe_merge(yv_batch* b, int n_images, hipStream_t s);
 
 // ---- the track half of the batch (yavo_batch_track.hip), as yv_batch_run and the view need it ----
 constexpr int kEvPerRun = 9;  // stage timing events per recorded run (yv_batch::events)
