@@ -386,6 +386,25 @@ int yv_batch_records_wait(yv_batch* b, void* stream);
  * Clears the tracks (set them again).  Declared in yavo_geom.h: the LK workspace API it uses. */
 int yv_batch_set_track_lk(yv_batch* b, int image_step, int win, int max_level, int max_count, double eps,
                           double min_eig);
+/* ---- track RANSAC: a P3P-RANSAC pose as each track's LM prior (opt-in, beyond the reference; off by default) ----
+ * With iters > 0 every following yv_batch_track runs yv_pnp_ransac_batch (yavo_geom.h: `iters` hypotheses from
+ * draws [iters][3], host, copied; threshold thr pixels; min_inliers) over each track's edges on the LM's stream just
+ * before the LM, in every overlap mode and in LK mode.  The LM's prior of a track is the RANSAC pose where one was found
+ * and the caller's d_priors entry otherwise; the LM itself is unchanged.  iters = 0 switches it off (the other arguments
+ * are ignored): not one launch or allocation more than before.  The arguments are checked as yv_pnp_ransac's
+ * (YV_ERR_INVALID); a call that changes the mode waits for the device (a track in flight reads the draws). */
+int yv_batch_set_track_ransac(yv_batch* b, int iters /* 0 = off */, double thr, int min_inliers,
+                              const uint32_t* draws);
+typedef struct yv_batch_ransac_view {
+    int n_tracks;
+    const double* pose;               /* [n_tracks][7] the LM's priors: the RANSAC pose, or the caller's prior */
+    const uint8_t* inlier;            /* [n_tracks][max_kp] by edge, zero where nothing was found */
+    const int32_t* inliers;           /* [n_tracks] */
+    const int32_t* found;             /* [n_tracks] */
+} yv_batch_ransac_view;
+/* Device views of the last yv_batch_track's RANSAC (complete when its LM is); YV_ERR_INVALID while the mode is off or
+ * no tracks are set. */
+int yv_batch_ransac_view_get(yv_batch* b, yv_batch_ransac_view* v);
 /* Per-stage device time of the runs since the last reset, when timing is enabled (HIP events recorded
  * on the run stream around every stage).  Stages: 0 detect (FAST + Harris + blur, one fused kernel),
  * 1 top-K + checkBoundry, 2 BRIEF, 3 match (with a match filter: both matcher launches), 4 Matches records +

@@ -86,6 +86,28 @@ int yv_f_ransac_batch(struct yv_ctx* ctx, const yv_match* d_matches, int64_t lis
                       int n_lists, const int32_t* d_samples, int64_t sample_stride, int iters, double thr,
                       double* d_F, int32_t* d_max_inliers, int32_t* d_found, void* stream);
 
+/* ---- P3P-RANSAC absolute pose (opt-in, beyond the reference: it has no solvePnPRansac) ----
+ * A pose from 3D-2D edges without a prior, and its inlier mask: `iters` hypotheses, hypothesis h from the edges
+ * draws[3 h + k] % n (two equal indices: no candidate), Grunert's P3P (up to 4 poses each), an edge an inlier of a pose
+ * iff its camera-frame z > 0 and the pose LM's edge error e has e0^2 + e1^2 < thr^2 (pixels); the pose with the most
+ * inliers wins, ties to the lowest hypothesis, then the lowest root.  *found = 1 iff that count >= min_inliers; otherwise
+ * pose is left untouched, inlier [n] is zero and *inliers = 0.  X, uv, K and pose as in yv_pose_lm, so the pose feeds it
+ * as the prior.  Bit-identical to tests/pnp_ransac_reference.py, which fixes the order of every operation.
+ * n <= 4096 (YV_ERR_CAPACITY past it), 1 <= iters <= 1024, min_inliers >= 4 (three points fit every candidate), thr
+ * finite and > 0, K finite: anything else is YV_ERR_INVALID, checked before the context. */
+int yv_pnp_ransac(struct yv_ctx* ctx, const double* X, const double* uv, int n, const double K[9],
+                  const uint32_t* draws, int iters, double thr, int min_inliers, double pose[7], uint8_t* inlier,
+                  int* inliers, int* found);
+/* The batched device-pointer form in yv_pose_lm_batch's layout (d_poses [p][7] in / out feeds it directly as priors;
+ * d_inlier by edge like d_outlier; d_draws [iters][3] serves every problem).  A problem of more than 4096 edges is
+ * solved on its first 4096 and its d_inlier bytes past them are left untouched.  n_problems <= 65535.  The hypothesis
+ * workspace belongs to the context: calls on one context must be serialised (as yv_f_ransac_batch); growing it
+ * synchronises the device. */
+int yv_pnp_ransac_batch(struct yv_ctx* ctx, int n_problems, const int32_t* d_offsets, const double* d_X,
+                        const double* d_uv, const double* d_K, const uint32_t* d_draws, int iters, double thr,
+                        int min_inliers, double* d_poses, uint8_t* d_inlier, int32_t* d_inliers, int32_t* d_found,
+                        void* stream);
+
 /* ---- cv::calcOpticalFlowPyrLK (src/LoopHandler.cc:372-375) ---------------------------
  * Restates OpenCV's pyramidal LK (flags 0: no initial flow) -- pyrDown pyramid (levels stop when the next one
  * would be <= win), Scharr derivatives, 14-bit bilinear windows, minEig test, Newton steps with the eps^2 and

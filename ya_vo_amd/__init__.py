@@ -81,6 +81,11 @@ class _BatchPyramidView(ctypes.Structure):
                 ("keypoints", ctypes.c_void_p * 8), ("level", ctypes.c_void_p), ("level_rc", ctypes.c_void_p)]
 
 
+class _BatchRansacView(ctypes.Structure):
+    _fields_ = [("n_tracks", ctypes.c_int), ("pose", ctypes.c_void_p), ("inlier", ctypes.c_void_p),
+                ("inliers", ctypes.c_void_p), ("found", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # symbol -> (restype, argtypes); the same list the C header declares (tests check they all resolve)
@@ -140,6 +145,8 @@ SIGNATURES = {
     "yv_batch_track_sync": (_I, [_P]),
     "yv_batch_records_wait": (_I, [_P, _P]),
     "yv_batch_set_track_lk": (_I, [_P, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double]),
+    "yv_batch_set_track_ransac": (_I, [_P, _I, ctypes.c_double, _I, _P]),
+    "yv_batch_ransac_view_get": (_I, [_P, ctypes.POINTER(_BatchRansacView)]),
 }
 
 
@@ -154,6 +161,8 @@ GEOM_SIGNATURES = {
     "yv_pose_lm_batch": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "yv_pose_gn_batch": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "yv_f_ransac_batch": (_I, [_P, _P, ctypes.c_int64, _P, _I, _P, ctypes.c_int64, _I, _D, _P, _P, _P, _P]),
+    "yv_pnp_ransac": (_I, [_P, _P, _P, _I, _P, _P, _I, _D, _I, _P, _P, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "yv_pnp_ransac_batch": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _D, _I, _P, _P, _P, _P, _P]),
     "yv_lk_create": (_I, [_P, _I, _I, _I, _I, _I, ctypes.POINTER(_P)]),
     "yv_lk_destroy": (None, [_P]),
     "yv_lk_levels": (_I, [_P]),
@@ -277,6 +286,12 @@ def lm_sum_mode(n_problems=None) -> int:
 def track_lm_sum_mode(n_tracks) -> int:
     """The batch track LM's edge-sum order (oracle sum_mode) for a batch of n_tracks tracks (yv_track_lm_sum_mode)."""
     return int(load_library().yv_track_lm_sum_mode(int(n_tracks)))
+
+
+def ransac_draws(iters: int, seed: int = 0) -> np.ndarray:
+    """The P3P-RANSAC draws table of a seed: uint32 [iters][3] from numpy.random.default_rng(seed) (one table serves
+    problems of any edge count: hypothesis h samples the edges draws[h] % n)."""
+    return np.random.default_rng(seed).integers(0, 2 ** 32, size=(int(iters), 3), dtype=np.uint32)
 
 
 def _check(status: int, what: str) -> None:
@@ -403,6 +418,34 @@ class _GeomMixin:
         _check(self.lib.yv_pose_lm(self.handle, _ptr(X), _ptr(uv), len(X), _ptr(_f64(K, 9)), _ptr(T), _ptr(out),
                                    ctypes.byref(inl)), "yv_pose_lm")
         return T, out[:len(X)].astype(bool), inl.value
+
+    def pnp_ransac(self, X, uv, K, draws=None, seed: int = 0, iters: int = 64, thr: float = 2.0,
+                   min_inliers: int = 12, pose=None):
+        """P3P-RANSAC absolute pose without a prior (yv_pnp_ransac) -> (pose [7], inlier [n] bool, inliers, found).
+        draws: uint32 [iters][3] (hypothesis h samples the edges draws[h] % n); None draws them from
+        numpy.random.default_rng(seed).  pose: what comes back when nothing is found (zeros if None).  The pose feeds
+        pose_lm as its prior."""
+        X, uv = _f64(X, (-1, 3)), _f64(uv, (-1, 2))
+        d = ransac_draws(iters, seed) if draws is None else np.ascontiguousarray(draws, np.uint32).reshape(-1, 3)
+        T = np.zeros(7) if pose is None else _f64(pose, 7).copy()
+        mask = np.zeros(max(len(X), 1), np.uint8)
+        inl, found = ctypes.c_int(), ctypes.c_int()
+        _check(self.lib.yv_pnp_ransac(self.handle, _ptr(X), _ptr(uv), len(X), _ptr(_f64(K, 9)), _ptr(d), len(d),
+                                      float(thr), int(min_inliers), _ptr(T), _ptr(mask), ctypes.byref(inl),
+                                      ctypes.byref(found)), "yv_pnp_ransac")
+        return T, mask[:len(X)].astype(bool), inl.value, bool(found.value)
+
+    def pnp_ransac_batch(self, n_problems: int, d_offsets: int, d_X: int, d_uv: int, d_K: int, d_draws: int,
+                         iters: int, d_poses: int, d_inlier: int, d_inliers: int, d_found: int, thr: float = 2.0,
+                         min_inliers: int = 12, stream: int = 0) -> None:
+        """yv_pnp_ransac_batch on device pointers, in yv_pose_lm_batch's layout: d_poses [p][7] (in / out) feeds it
+        as the priors; d_draws uint32 [iters][3] serves every problem."""
+        _check(self.lib.yv_pnp_ransac_batch(self.handle, n_problems, ctypes.c_void_p(d_offsets), ctypes.c_void_p(d_X),
+                                            ctypes.c_void_p(d_uv), ctypes.c_void_p(d_K), ctypes.c_void_p(d_draws),
+                                            int(iters), float(thr), int(min_inliers), ctypes.c_void_p(d_poses),
+                                            ctypes.c_void_p(d_inlier), ctypes.c_void_p(d_inliers),
+                                            ctypes.c_void_p(d_found), ctypes.c_void_p(stream) if stream else None),
+               "yv_pnp_ransac_batch")
 
     def pose_gn(self, X, uv, K, pose):
         """bundleAdjustmentGaussNewton -> (pose [7], accepted iterations)."""
@@ -782,6 +825,27 @@ class Batch:
         """LK tracking mode (yv_batch_set_track_lk): tracks become {stereo pair of frame k-1, image of frame k}."""
         _check(self.lib.yv_batch_set_track_lk(self.handle, image_step, win, max_level, max_count, eps, min_eig),
                "yv_batch_set_track_lk")
+
+    def set_track_ransac(self, iters: int, thr: float = 2.0, min_inliers: int = 12, seed: int = 0,
+                         draws=None) -> None:
+        """The track RANSAC of the following track calls (yv_batch_set_track_ransac): a P3P-RANSAC pose over each
+        track's edges becomes its LM prior where one is found (the caller's prior otherwise).  iters = 0 (the default
+        state) switches it off.  draws: uint32 [iters][3]; None draws them from numpy.random.default_rng(seed)."""
+        if not iters:
+            _check(self.lib.yv_batch_set_track_ransac(self.handle, 0, 0.0, 0, None), "yv_batch_set_track_ransac")
+            return
+        d = ransac_draws(iters, seed) if draws is None else np.ascontiguousarray(draws, np.uint32).reshape(-1, 3)
+        if len(d) != iters:
+            raise ValueError("draws must be [iters][3]")
+        _check(self.lib.yv_batch_set_track_ransac(self.handle, int(iters), float(thr), int(min_inliers), _ptr(d)),
+               "yv_batch_set_track_ransac")
+
+    def ransac_view(self) -> _BatchRansacView:
+        """Device arrays of the last track's RANSAC (yv_batch_ransac_view_get; with set_track_ransac on): pose
+        [n_tracks][7] float64 (the LM's priors), inlier [n_tracks][max_kp] uint8, inliers and found [n_tracks] int32."""
+        v = _BatchRansacView()
+        _check(self.lib.yv_batch_ransac_view_get(self.handle, ctypes.byref(v)), "yv_batch_ransac_view_get")
+        return v
 
     def track_sync(self) -> None:
         _check(self.lib.yv_batch_track_sync(self.handle), "yv_batch_track_sync")

@@ -55,6 +55,48 @@ TrackSrc track_src(const yv_batch* b) {
             sub && (b->subpix_flags & YV_SUBPIX_DROP_EDGE) != 0};
 }
 
+// buffer k of the track RANSAC's outputs
+struct RansacSlice {
+    double* pose;
+    uint8_t* inlier;
+    int32_t* inliers;
+    int32_t* found;
+};
+
+RansacSlice ransac_slice(const yv_batch* b, int k) {
+    const size_t nt = (size_t)b->ransac_tracks, nk = (size_t)b->max_kp;
+    return {b->ransac_pose + k * nt * 7, b->ransac_inlier + k * nt * nk, b->ransac_inliers + k * nt,
+            b->ransac_found + k * nt};
+}
+
+// The track RANSAC's buffers for max_tracks tracks and ransac_iters hypotheses (a no-op while the mode is off, no tracks
+// were set or they already fit).  The caller has drained the streams a track runs on.
+int ensure_ransac(yv_batch* b) {
+    if (b->ransac_iters == 0 || b->max_tracks == 0) return YV_OK;
+    if (b->max_tracks > 65535) return YV_ERR_CAPACITY;  // a track per workgroup row of the grid
+    if (b->ransac_tracks >= b->max_tracks && b->ransac_iters_cap >= b->ransac_iters) return YV_OK;
+    b->mem.release(b->ransac_ws, b->ransac_pose, b->ransac_inlier, b->ransac_inliers, b->ransac_found);
+    b->ransac_tracks = 0;
+    const size_t nt = (size_t)b->max_tracks, nk = (size_t)b->max_kp;
+    const int cap = std::max(b->ransac_iters_cap, b->ransac_iters);
+    int rc = YV_OK;
+    rc |= b->mem.alloc(&b->ransac_ws, yavo::pnp_ransac_ws_bytes(b->max_tracks, cap));
+    rc |= b->mem.alloc(&b->ransac_pose, kEdgeBufs * nt * 7);
+    rc |= b->mem.alloc(&b->ransac_inlier, kEdgeBufs * nt * nk);
+    rc |= b->mem.alloc(&b->ransac_inliers, kEdgeBufs * nt);
+    rc |= b->mem.alloc(&b->ransac_found, kEdgeBufs * nt);
+    if (rc != YV_OK) return YV_ERR_HIP;
+    hipStream_t s = b->ctx->stream;
+    YV_HIP(hipMemsetAsync(b->ransac_pose, 0, sizeof(double) * kEdgeBufs * nt * 7, s));
+    YV_HIP(hipMemsetAsync(b->ransac_inlier, 0, kEdgeBufs * nt * nk, s));
+    YV_HIP(hipMemsetAsync(b->ransac_inliers, 0, sizeof(int32_t) * kEdgeBufs * nt, s));
+    YV_HIP(hipMemsetAsync(b->ransac_found, 0, sizeof(int32_t) * kEdgeBufs * nt, s));
+    YV_HIP(hipStreamSynchronize(s));
+    b->ransac_tracks = b->max_tracks;
+    b->ransac_iters_cap = cap;
+    return YV_OK;
+}
+
 // The pose LM (and the map block) of one track. Overlap: on the side stream after the edge build (ev_edges[k]);
 // otherwise on `s`, in order.
 int launch_lm(yv_batch* b, const yv_batch::DeferredLM& L, hipStream_t s) {
@@ -68,7 +110,18 @@ int launch_lm(yv_batch* b, const yv_batch::DeferredLM& L, hipStream_t s) {
         ls = b->side;
     }
     if (L.ev) YV_HIP(hipEventRecord(L.ev[7], ls));
-    yavo::launch_track_pose(b->n_tracks, e.count, b->max_kp, e.X, e.uv, b->track_K, L.priors, L.poses, e.outlier,
+    const double* priors = L.priors;
+    if (b->ransac_iters > 0) {
+        // the track RANSAC on the LM's stream, over the same edge buffer and after the same waits: whatever orders the
+        // LM against the build before it and the build kEdgeBufs tracks later (ev_lm[k], recorded below) orders this
+        // too.  It reads the caller's priors here, where the LM would, and the LM reads buffer k's priors after it
+        const RansacSlice r = ransac_slice(b, k);
+        yavo::launch_pnp_ransac(nullptr, e.count, b->max_kp, b->n_tracks, e.X, e.uv, b->track_K,
+                                b->ransac_draws, b->ransac_iters, b->ransac_thr, b->ransac_min, L.priors, r.pose,
+                                r.inlier, r.inliers, r.found, b->ransac_ws, ls);
+        priors = r.pose;
+    }
+    yavo::launch_track_pose(b->n_tracks, e.count, b->max_kp, e.X, e.uv, b->track_K, priors, L.poses, e.outlier,
                             e.inliers, ls);
     if (L.ev) {
         YV_HIP(hipEventRecord(L.ev[8], ls));
@@ -257,6 +310,8 @@ int yv_batch_set_tracks(yv_batch* b, const int32_t* tracks, int n_tracks, const 
         b->lk_ev_pending[0] = b->lk_ev_pending[1] = false;
         if (rc != YV_OK) return YV_ERR_HIP;
         b->max_tracks = n_tracks;
+        rc = ensure_ransac(b);  // (the streams a track runs on were drained above)
+        if (rc != YV_OK) return rc;
     }
     if (n_tracks > 0) {
         std::vector<double> Ks(9 * (size_t)n_tracks);
@@ -364,6 +419,44 @@ int yv_batch_records_wait(yv_batch* b, void* stream) {
     if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
     // (the flag stays: the next writer of the keypoints still joins on its own stream)
     if (b->records_pending) YV_HIP(hipStreamWaitEvent(reinterpret_cast<hipStream_t>(stream), b->ev_records, 0));
+    return YV_OK;
+}
+
+int yv_batch_set_track_ransac(yv_batch* b, int iters, double thr, int min_inliers, const uint32_t* draws) {
+    if (!b || iters < 0) return YV_ERR_INVALID;
+    if (iters > 0 && (iters > yavo::kPnpMaxIters || min_inliers < 4 || !std::isfinite(thr) || !(thr > 0) || !draws))
+        return YV_ERR_INVALID;
+    if (iters == 0 && b->ransac_iters == 0) return YV_OK;  // off stays off: nothing to wait for
+    if (set_device(b->ctx) != YV_OK) return YV_ERR_HIP;
+    // a deferred LM belongs to the mode it was issued in; a track in flight, on whichever stream the caller named,
+    // reads the draws and the workspace
+    if (flush_deferred(b) != YV_OK) return YV_ERR_HIP;
+    YV_HIP(hipDeviceSynchronize());
+    if (iters == 0) {
+        b->ransac_iters = 0;
+        return YV_OK;
+    }
+    if (!b->ransac_draws && b->mem.alloc(&b->ransac_draws, 3 * (size_t)yavo::kPnpMaxIters) != YV_OK)
+        return YV_ERR_HIP;
+    YV_HIP(hipMemcpyAsync(b->ransac_draws, draws, sizeof(uint32_t) * 3 * (size_t)iters, hipMemcpyHostToDevice,
+                          b->ctx->stream));
+    YV_HIP(hipStreamSynchronize(b->ctx->stream));
+    b->ransac_iters = iters;
+    b->ransac_thr = thr;
+    b->ransac_min = min_inliers;
+    const int rc = ensure_ransac(b);
+    if (rc != YV_OK) b->ransac_iters = 0;
+    return rc;
+}
+
+int yv_batch_ransac_view_get(yv_batch* b, yv_batch_ransac_view* v) {
+    if (!b || !v || b->ransac_iters == 0 || b->ransac_tracks == 0) return YV_ERR_INVALID;
+    const RansacSlice r = ransac_slice(b, b->tbuf);
+    v->n_tracks = b->n_tracks;
+    v->pose = r.pose;
+    v->inlier = r.inlier;
+    v->inliers = r.inliers;
+    v->found = r.found;
     return YV_OK;
 }
 

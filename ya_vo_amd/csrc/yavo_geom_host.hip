@@ -210,6 +210,88 @@ int yv_f_ransac_batch(yv_ctx* ctx, const yv_match* d_matches, int64_t list_strid
     return check_launch();
 }
 
+// what both P3P-RANSAC entry points check before they look at the context
+static int pnp_args_check(int iters, double thr, int min_inliers) {
+    if (iters < 1 || iters > yavo::kPnpMaxIters || min_inliers < 4 || !std::isfinite(thr) || !(thr > 0))
+        return YV_ERR_INVALID;
+    return YV_OK;
+}
+
+int yv_pnp_ransac(yv_ctx* ctx, const double* X, const double* uv, int n, const double K[9], const uint32_t* draws,
+                  int iters, double thr, int min_inliers, double pose[7], uint8_t* inlier, int* inliers, int* found) {
+    if (!K || !draws || !pose || !inliers || !found || n < 0 || (n > 0 && (!X || !uv || !inlier)))
+        return YV_ERR_INVALID;
+    if (pnp_args_check(iters, thr, min_inliers) != YV_OK) return YV_ERR_INVALID;
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(K[i])) return YV_ERR_INVALID;
+    if (n > 4096) return YV_ERR_CAPACITY;
+    if (!ctx) return YV_ERR_INVALID;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = ctx->stream;
+    Arena a{ctx};
+    int32_t *doff, *dinl, *dfound;
+    uint32_t* ddraws;
+    double *dX, *duv, *dK, *dP;
+    uint8_t *dmask, *dws;
+    a.add(&dX, 3 * (size_t)std::max(n, 1));  // read by every candidate's count: on the device
+    a.add(&duv, 2 * (size_t)std::max(n, 1));
+    a.add(&dws, yavo::pnp_ransac_ws_bytes(1, iters));
+    a.add_host(&doff, 2);  // read once, or written once: in the pinned mirror
+    a.add_host(&ddraws, 3 * (size_t)iters);
+    a.add_host(&dK, 9);
+    a.add_host(&dP, 7);
+    a.add_host(&dmask, (size_t)std::max(n, 1));
+    a.add_host(&dinl, 1);
+    a.add_host(&dfound, 1);
+    if (a.commit() != YV_OK) return YV_ERR_HIP;
+    const int32_t off2[2] = {0, n};
+    a.in(doff, off2, 2 * sizeof(int32_t));
+    if (n > 0) {
+        a.in(dX, X, sizeof(double) * 3 * (size_t)n);
+        a.in(duv, uv, sizeof(double) * 2 * (size_t)n);
+    }
+    a.in(ddraws, draws, sizeof(uint32_t) * 3 * (size_t)iters);
+    a.in(dK, K, sizeof(double) * 9);
+    a.in(dP, pose, sizeof(double) * 7);  // untouched when nothing is found
+    YV_HIP(a.upload(s));
+    yavo::launch_pnp_ransac(doff, nullptr, 0, 1, dX, duv, dK, ddraws, iters, thr, min_inliers, nullptr, dP, dmask,
+                            dinl, dfound, dws, s);
+    if (check_launch() != YV_OK) return YV_ERR_HIP;
+    a.out(pose, dP, sizeof(double) * 7);
+    if (n > 0) a.out(inlier, dmask, (size_t)n);
+    a.out(inliers, dinl, sizeof(int32_t));
+    a.out(found, dfound, sizeof(int32_t));
+    YV_HIP(a.fetch(s));
+    return YV_OK;
+}
+
+int yv_pnp_ransac_batch(yv_ctx* ctx, int n_problems, const int32_t* d_offsets, const double* d_X, const double* d_uv,
+                        const double* d_K, const uint32_t* d_draws, int iters, double thr, int min_inliers,
+                        double* d_poses, uint8_t* d_inlier, int32_t* d_inliers, int32_t* d_found, void* stream) {
+    if (n_problems < 0 || (n_problems > 0 && (!d_offsets || !d_X || !d_uv || !d_K || !d_draws || !d_poses ||
+                                              !d_inlier || !d_inliers || !d_found)))
+        return YV_ERR_INVALID;
+    if (pnp_args_check(iters, thr, min_inliers) != YV_OK) return YV_ERR_INVALID;
+    if (n_problems > 65535) return YV_ERR_CAPACITY;
+    if (!ctx) return YV_ERR_INVALID;
+    if (n_problems == 0) return YV_OK;
+    if (set_device(ctx) != YV_OK) return YV_ERR_HIP;
+    StageScope stage_scope(ctx);
+    hipStream_t s = stream ? reinterpret_cast<hipStream_t>(stream) : ctx->stream;
+    const size_t need = yavo::pnp_ransac_ws_bytes(n_problems, iters);
+    if (need > ctx->pnp_ws_cap) {  // grown outside any timed loop; earlier launches that use it have finished
+        YV_HIP(hipDeviceSynchronize());
+        ctx->mem.release(ctx->pnp_ws);
+        ctx->pnp_ws_cap = 0;
+        if (ctx->mem.alloc(&ctx->pnp_ws, need) != YV_OK) return YV_ERR_HIP;
+        ctx->pnp_ws_cap = need;
+    }
+    yavo::launch_pnp_ransac(d_offsets, nullptr, 0, n_problems, d_X, d_uv, d_K, d_draws, iters, thr, min_inliers,
+                            nullptr, d_poses, d_inlier, d_inliers, d_found, ctx->pnp_ws, s);
+    return check_launch();
+}
+
 // Test entry point (tests/test_gpu_pose_degenerate.py; like yv_debug_xlane not part of the public headers): the batch's
 // track LM alone (launch_track_pose: the fixed-stride layout, track t owns d_counts[t] edges from t * stride) on device
 // buffers; d_priors [n][7] is read, d_poses [n][7] written.

@@ -149,6 +149,8 @@ struct yv_ctx {
     uint8_t* scratch_hd = nullptr;                            // the mirror's address for kernels (zero-copy regions)
     void* fr_ws = nullptr;                                    // yv_f_ransac_batch's hypothesis workspace
     size_t fr_ws_cap = 0;
+    void* pnp_ws = nullptr;                                   // yv_pnp_ransac_batch's hypothesis workspace
+    size_t pnp_ws_cap = 0;
     // yv_calc_optical_flow_pyr_lk's pyramid workspace, kept between calls (creating and destroying it per call
     // costs two hipMalloc / hipFree pairs and a device-wide synchronisation per tracked frame)
     yv_lk* lk_cache = nullptr;
@@ -316,6 +318,18 @@ struct yv_batch {
     int lk_set = 0;
     hipEvent_t ev_lk[2] = {};
     bool lk_ev_pending[2] = {false, false};
+    // track RANSAC (yv_batch_set_track_ransac): 0 iterations = off.  Its outputs come kEdgeBufs times like the edge
+    // buffers (buffer k: ransac_slice), so a view or a deferred LM of track i still reads its own while track i + 1's
+    // RANSAC runs; the hypothesis workspace is one, every RANSAC runs in order on the LM's stream.  Sized for max_tracks
+    // by ensure_ransac (the call that switches the mode on, or the yv_batch_set_tracks that grows the tracks)
+    int ransac_iters = 0, ransac_min = 0, ransac_tracks = 0, ransac_iters_cap = 0;
+    double ransac_thr = 0;
+    uint32_t* ransac_draws = nullptr;  // [ransac_iters_cap][3]
+    void* ransac_ws = nullptr;
+    double* ransac_pose = nullptr;     // [kEdgeBufs][ransac_tracks][7] the LM's priors
+    uint8_t* ransac_inlier = nullptr;  // [kEdgeBufs][ransac_tracks][max_kp]
+    int32_t* ransac_inliers = nullptr; // [kEdgeBufs][ransac_tracks]
+    int32_t* ransac_found = nullptr;   // [kEdgeBufs][ransac_tracks]
     const uint8_t* run_images = nullptr;  // the last yv_batch_run's images (LK reads them)
     int run_n = 0, run_stride = 0;
     int64_t run_pitch = 0;

@@ -270,6 +270,18 @@ void launch_track_pose(int n_tracks, const int32_t* edge_count, int stride, cons
                        const double* edge_uv, const double* K, const double* priors, double* poses,
                        uint8_t* edge_outlier, int32_t* inliers, hipStream_t s);
 
+// ---- P3P-RANSAC absolute pose (yavo_pnp.hip) ----
+constexpr int kPnpMaxIters = 1024;  // hypotheses per problem (4 candidate poses each)
+// device workspace of launch_pnp_ransac: [n_problems][iters] hypotheses' 4 poses, inlier counts and root masks
+size_t pnp_ransac_ws_bytes(int n_problems, int iters);
+// Problem p's edges as the pose LM addresses them: [offsets[p], offsets[p + 1]), or with counts (the track layout)
+// counts[p] edges from p * stride; the first 4096.
+// draws [iters][3] serves every problem.  init (optional [p][7]): poses[p] where nothing is found; nullptr leaves it.
+void launch_pnp_ransac(const int32_t* offsets, const int32_t* counts, int stride, int n_problems,
+                       const double* X, const double* uv, const double* K, const uint32_t* draws, int iters,
+                       double thr, int min_inliers, const double* init, double* poses, uint8_t* inlier,
+                       int32_t* inliers, int32_t* found, void* ws, hipStream_t s);
+
 // ---- track composition (yavo_track.hip): a run's stereo and temporal matches into the pose LM's edges ----
 // What the track kernels read: the run's pair list, keypoints ([slot][max_kp]) and match records ([pair][max_kp]), the
 // tracks' K ([n_tracks][9]) and the right camera's pose T_right ([7]).  The rest is optional, [pair][max_kp]:

@@ -190,7 +190,8 @@ class SequenceFrontend:
 
     def __init__(self, ctx, chunk: int, K, T_right, n_fixed: int = 2, ba_iters: int = 10,
                  H: int = 376, W: int = 1241, max_kp: int = 2000, match_thr: int = 20, device_window: bool = True,
-                 ba_priority: int = 0, expected_frames: int = 0, ba_stream=None, multiview: bool = False):
+                 ba_priority: int = 0, expected_frames: int = 0, ba_stream=None, multiview: bool = False,
+                 ransac=None):
         """device_window: the BA window is recorded, assembled and written back on the device (yv_ba_window_*,
         no per-chunk read-back); False: the host assembly below (window_problem / apply_window), kept as the
         restatement the device path is checked against. ba_priority: the BA stream's priority (torch's convention:
@@ -198,7 +199,10 @@ class SequenceFrontend:
         sequence length when known (the device window's record store is sized for it up front instead of growing by
         doubling, which synchronises the device inside the loop). multiview: landmarks the temporal matches follow over
         several frames enter the window once, observed by every frame of their chain (window_problem_tracks; on the
-        device yv_ba_window_set_multiview), instead of once per frame with two observations."""
+        device yv_ba_window_set_multiview), instead of once per frame with two observations. ransac: None (the
+        default: every track's LM starts from the identity prior, as before) or the keyword arguments of
+        Batch.set_track_ransac (iters, thr, min_inliers, seed): a P3P-RANSAC pose over each track's edges is its LM
+        prior where one is found."""
         import torch
         from . import Batch, BaWindow, BundleAdjuster
         if chunk < 2 or n_fixed < 1:
@@ -219,6 +223,8 @@ class SequenceFrontend:
             tracks.append((2 * k + 1, 2 * k))
         self.batch.set_pairs(pairs)
         self.batch.set_tracks(tracks, self.K, T_right)
+        if ransac is not None:
+            self.batch.set_track_ransac(**dict(ransac))
         dev = torch.device("cuda", ctx.device)
         self.bb = ymap.block_bytes(chunk, max_kp)
         self.d_block = torch.zeros(self.bb, dtype=torch.uint8, device=dev)
