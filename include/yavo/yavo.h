@@ -452,5 +452,6 @@ int yv_batch_view_get(yv_batch* b, yv_batch_view* view);
 #endif
 
 #include "yavo_geom.h"
+#include "yavo_bow.h"
 
 #endif /* YAVO_H */

@@ -86,6 +86,16 @@ class _BatchRansacView(ctypes.Structure):
                 ("inliers", ctypes.c_void_p), ("found", ctypes.c_void_p)]
 
 
+class _BowView(ctypes.Structure):
+    _fields_ = [("n_words", ctypes.c_int), ("w_pad", ctypes.c_int), ("max_entries", ctypes.c_int),
+                ("max_queries", ctypes.c_int), ("max_kp", ctypes.c_int), ("n_entries", ctypes.c_int),
+                ("n_queries", ctypes.c_int), ("vectors", ctypes.c_void_p), ("norm2", ctypes.c_void_p),
+                ("frame_id", ctypes.c_void_p), ("q_word", ctypes.c_void_p), ("q_dist", ctypes.c_void_p),
+                ("q_vectors", ctypes.c_void_p), ("q_norm2", ctypes.c_void_p), ("dots", ctypes.c_void_p),
+                ("cand_entry", ctypes.c_void_p), ("cand_score", ctypes.c_void_p), ("cand_dot", ctypes.c_void_p),
+                ("cand_count", ctypes.c_void_p)]
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # symbol -> (restype, argtypes); the same list the C header declares (tests check they all resolve)
@@ -204,6 +214,26 @@ GEOM_SIGNATURES = {
     "yv_track_lm_sum_mode": (_I, [_I]),
 }
 
+# include/yavo/yavo_bow.h (the bag-of-binary-words keyframe index; ya_vo_amd/bow.py wraps it)
+_I64 = ctypes.c_int64
+BOW_SIGNATURES = {
+    "yv_bow_create": (_I, [_P, _I, _P, _P, _I, _I, _I, ctypes.POINTER(_P)]),
+    "yv_bow_destroy": (None, [_P]),
+    "yv_bow_reset": (_I, [_P]),
+    "yv_bow_count": (_I, [_P, ctypes.POINTER(_I)]),
+    "yv_bow_words": (_I, [_P, _P, _I, _P, _P]),
+    "yv_bow_vector": (_I, [_P, _P, _I, _P, _P]),
+    "yv_bow_add": (_I, [_P, _P, _I, _I64]),
+    "yv_bow_query": (_I, [_P, _P, _I, _I64, _I64, _I, _P, _P, _P, _P, ctypes.POINTER(_I)]),
+    "yv_bow_add_batch": (_I, [_P, _P, _P, _P, _I, _P]),
+    "yv_bow_query_batch": (_I, [_P, _P, _P, _P, _I, _I64, _I, _P]),
+    "yv_bow_view_get": (_I, [_P, ctypes.POINTER(_BowView)]),
+    "yv_bow_candidates_copy": (_I, [_P, _I, _P, _P, _P, _P, _P]),
+    # measurement entry points of tools/bench_bow.py (not in the public headers)
+    "yv_debug_bow_stages": (_I, [_P, _I]),
+    "yv_debug_match_keys": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
+}
+
 # include/yavo/yavo_map.h (the shared map; ya_vo_amd/map.py wraps the block layout)
 MAP_SIGNATURES = {
     "yv_map_block_bytes": (ctypes.c_int64, [_I, _I]),
@@ -266,7 +296,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         except ImportError:
             pass
     lib = ctypes.CDLL(path)
-    tables = (SIGNATURES, GEOM_SIGNATURES, IO_SIGNATURES, MAP_SIGNATURES)
+    tables = (SIGNATURES, GEOM_SIGNATURES, IO_SIGNATURES, MAP_SIGNATURES, BOW_SIGNATURES)
     for name, (res, args) in [kv for t in tables for kv in t.items()]:
         fn = getattr(lib, name)
         fn.restype = res

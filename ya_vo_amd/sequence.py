@@ -191,7 +191,7 @@ class SequenceFrontend:
     def __init__(self, ctx, chunk: int, K, T_right, n_fixed: int = 2, ba_iters: int = 10,
                  H: int = 376, W: int = 1241, max_kp: int = 2000, match_thr: int = 20, device_window: bool = True,
                  ba_priority: int = 0, expected_frames: int = 0, ba_stream=None, multiview: bool = False,
-                 ransac=None):
+                 ransac=None, loop=None):
         """device_window: the BA window is recorded, assembled and written back on the device (yv_ba_window_*,
         no per-chunk read-back); False: the host assembly below (window_problem / apply_window), kept as the
         restatement the device path is checked against. ba_priority: the BA stream's priority (torch's convention:
@@ -202,7 +202,12 @@ class SequenceFrontend:
         device yv_ba_window_set_multiview), instead of once per frame with two observations. ransac: None (the
         default: every track's LM starts from the identity prior, as before) or the keyword arguments of
         Batch.set_track_ransac (iters, thr, min_inliers, seed): a P3P-RANSAC pose over each track's edges is its LM
-        prior where one is found."""
+        prior where one is found. loop: None (the default: not one call more than before) or a dict {index, every,
+        exclude, top_k, min_score} (index: a ya_vo_amd.bow.BowIndex with max_kp >= this front end's and max_queries >=
+        chunk): after each chunk's run the left image of every frame with frame % every == 0 is queried against the
+        index (exclusion window `exclude` frames, `top_k` candidates) and then added to it, both on the context stream
+        before the next run; candidates with score >= min_score accumulate in loop_candidates as (frame, entry_frame,
+        score), read back when flush / records synchronise."""
         import torch
         from . import Batch, BaWindow, BundleAdjuster
         if chunk < 2 or n_fixed < 1:
@@ -258,6 +263,18 @@ class SequenceFrontend:
             self.win.reserve(expected_frames)
         self._records: Dict[int, FrameRecord] = {}
         self.next_frame = 0
+        self.loop = None
+        self.loop_candidates: List[Tuple[int, int, float]] = []
+        if loop is not None:
+            self.loop = dict(loop)
+            self.loop.setdefault("every", 1)
+            self.loop.setdefault("exclude", 0)
+            self.loop.setdefault("top_k", 4)
+            self.loop.setdefault("min_score", 0.0)
+            if self.loop["every"] < 1:
+                raise ValueError("loop: every < 1")
+            self._loop_dev = dev
+            self._loop_pending = []  # (frames, d_entry, d_score, d_count) per chunk, until the next flush
         self.ba_log: List[Tuple[int, int, float, float]] = []  # (last frame, iterations, chi2 first, chi2 last)
 
     def close(self) -> None:
@@ -293,6 +310,8 @@ class SequenceFrontend:
         self.batch.run(d_images.data_ptr(), 2 * n, self.W, self.H * self.W, self.match_thr,
                        carry_from=2 * (n - 1))
         self.batch.track_map(self.d_prior.data_ptr(), self.d_poses.data_ptr(), first, 1, self.d_block.data_ptr(), n)
+        if self.loop is not None:
+            self._loop_chunk(first)
         if self.win is not None:
             return self._process_chunk_device(first, t0, seconds)
         t1 = time.perf_counter()
@@ -357,9 +376,42 @@ class SequenceFrontend:
         if solved:
             self.ba_log.append((self._ba_last, it, float(log[0]), float(log[-1])))
 
+    def _loop_chunk(self, first: int) -> None:
+        """Query, then add, the left images of this chunk's frames with frame % every == 0 (the query comes first: a
+        frame never finds itself), on the context stream; the candidate lists go to device arrays kept until flush."""
+        import torch
+        lp = self.loop
+        ks = [k for k in range(self.chunk) if (first + k) % lp["every"] == 0]
+        if not ks:
+            return
+        slots, frames = [2 * k for k in ks], [first + k for k in ks]
+        idx = lp["index"]
+        idx.query_batch(self.batch, slots, frames, lp["exclude"], lp["top_k"])
+        d_entry = torch.empty((len(ks), 16), dtype=torch.int32, device=self._loop_dev)
+        d_score = torch.empty((len(ks), 16), dtype=torch.float64, device=self._loop_dev)
+        d_count = torch.empty(len(ks), dtype=torch.int32, device=self._loop_dev)
+        idx.candidates_copy(len(ks), d_entry.data_ptr(), d_score.data_ptr(), 0, d_count.data_ptr())
+        idx.add_batch(self.batch, slots, frames)
+        self._loop_pending.append((frames, d_entry, d_score, d_count))
+
+    def _loop_collect(self) -> None:
+        """The pending chunks' candidate lists into loop_candidates (waits for the context stream)."""
+        if self.loop is None or not self._loop_pending:
+            return
+        self.ctx.sync()
+        ef, lo = self.loop["index"].entry_frames, self.loop["min_score"]
+        for frames, d_entry, d_score, d_count in self._loop_pending:
+            e, sc, cnt = d_entry.cpu().numpy(), d_score.cpu().numpy(), d_count.cpu().numpy()
+            for q, f in enumerate(frames):
+                for k in range(int(cnt[q])):
+                    if sc[q, k] >= lo:
+                        self.loop_candidates.append((f, ef[int(e[q, k])], float(sc[q, k])))
+        self._loop_pending = []
+
     def flush(self, seconds: Dict[str, float] = None) -> None:
         """The last chunk's BA window (process_chunk runs each window one chunk late)."""
         import time
+        self._loop_collect()
         if self._ba_pending and self.win is not None:
             t0 = time.perf_counter()
             self._local_ba_device_end()
