@@ -453,5 +453,6 @@ int yv_batch_view_get(yv_batch* b, yv_batch_view* view);
 
 #include "yavo_geom.h"
 #include "yavo_bow.h"
+#include "yavo_loop.h"
 
 #endif /* YAVO_H */

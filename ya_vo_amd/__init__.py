@@ -96,6 +96,22 @@ class _BowView(ctypes.Structure):
                 ("cand_count", ctypes.c_void_p)]
 
 
+class _LoopView(ctypes.Structure):
+    _fields_ = [("max_entries", ctypes.c_int), ("max_problems", ctypes.c_int), ("max_kp", ctypes.c_int),
+                ("n_entries", ctypes.c_int), ("n_problems", ctypes.c_int), ("desc", ctypes.c_void_p),
+                ("pos", ctypes.c_void_p), ("X", ctypes.c_void_p), ("has", ctypes.c_void_p),
+                ("kp_count", ctypes.c_void_p), ("frame_id", ctypes.c_void_p), ("results", ctypes.c_void_p),
+                ("edge_X", ctypes.c_void_p), ("edge_uv", ctypes.c_void_p), ("edge_query", ctypes.c_void_p),
+                ("edge_train", ctypes.c_void_p), ("ransac_inlier", ctypes.c_void_p), ("lm_outlier", ctypes.c_void_p),
+                ("edge_count", ctypes.c_void_p)]
+
+
+# yv_loop_result (80 B): one verification problem's outcome (include/yavo/yavo_loop.h)
+LOOP_RESULT_DTYPE = np.dtype([("entry", "<i4"), ("n_kept", "<i4"), ("n_edges", "<i4"), ("ransac_inliers", "<i4"),
+                              ("lm_inliers", "<i4"), ("verified", "<i4"), ("pose", "<f8", (7,))])
+assert LOOP_RESULT_DTYPE.itemsize == 80
+
+
 _lib: Optional[ctypes.CDLL] = None
 
 # symbol -> (restype, argtypes); the same list the C header declares (tests check they all resolve)
@@ -234,6 +250,25 @@ BOW_SIGNATURES = {
     "yv_debug_match_keys": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P]),
 }
 
+# include/yavo/yavo_loop.h (the keyframe store and the verification of candidates; ya_vo_amd/loop.py wraps it)
+LOOP_SIGNATURES = {
+    "yv_loop_create": (_I, [_P, _P, _P, _I, _I, _I, ctypes.POINTER(_P)]),
+    "yv_loop_destroy": (None, [_P]),
+    "yv_loop_reset": (_I, [_P]),
+    "yv_loop_count": (_I, [_P, ctypes.POINTER(_I)]),
+    "yv_loop_set_params": (_I, [_P, _I, _I, _I, _I, _I, _P, _D, _I]),
+    "yv_loop_lm_sum_mode": (_I, [_I]),
+    "yv_loop_add": (_I, [_P, _P, _I, _P, _P, _I64]),
+    "yv_loop_verify": (_I, [_P, _P, _I, _P, _I, _P]),
+    "yv_loop_add_batch": (_I, [_P, _P, _P, _P, _P, _I, _P]),
+    "yv_loop_verify_batch": (_I, [_P, _P, _P, _I, _P, _P, _I, _P]),
+    "yv_loop_view_get": (_I, [_P, ctypes.POINTER(_LoopView)]),
+    "yv_loop_results_copy": (_I, [_P, _I, _P, _P]),
+    # measurement entry points of tools/bench_loop.py (not in the public headers)
+    "yv_debug_loop_stages": (_I, [_P, _I]),
+    "yv_debug_loop_match": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _P]),
+}
+
 # include/yavo/yavo_map.h (the shared map; ya_vo_amd/map.py wraps the block layout)
 MAP_SIGNATURES = {
     "yv_map_block_bytes": (ctypes.c_int64, [_I, _I]),
@@ -296,7 +331,7 @@ def load_library(path: str = LIB_PATH) -> ctypes.CDLL:
         except ImportError:
             pass
     lib = ctypes.CDLL(path)
-    tables = (SIGNATURES, GEOM_SIGNATURES, IO_SIGNATURES, MAP_SIGNATURES, BOW_SIGNATURES)
+    tables = (SIGNATURES, GEOM_SIGNATURES, IO_SIGNATURES, MAP_SIGNATURES, BOW_SIGNATURES, LOOP_SIGNATURES)
     for name, (res, args) in [kv for t in tables for kv in t.items()]:
         fn = getattr(lib, name)
         fn.restype = res

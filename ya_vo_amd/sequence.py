@@ -24,6 +24,7 @@ from typing import Dict, List, Tuple
 
 import numpy as np
 
+from . import LOOP_RESULT_DTYPE
 from . import map as ymap
 
 IDENTITY = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
@@ -207,7 +208,13 @@ class SequenceFrontend:
         chunk): after each chunk's run the left image of every frame with frame % every == 0 is queried against the
         index (exclusion window `exclude` frames, `top_k` candidates) and then added to it, both on the context stream
         before the next run; candidates with score >= min_score accumulate in loop_candidates as (frame, entry_frame,
-        score), read back when flush / records synchronise."""
+        score), read back when flush / records synchronise. The dict's optional key verify (a
+        ya_vo_amd.loop.LoopVerifier with set_params called, max_kp >= this front end's, max_problems >= chunk * top_k
+        and the entries of the index, i.e. both empty or filled alike) adds the geometric verification: after the
+        query, the candidate rows are verified on the device against the stored keyframes, then the chunk's frames
+        are added to the store with their stereo landmarks; the verified candidates that also passed min_score
+        accumulate in loop_closures as (frame, entry_frame, pose[7], lm_inliers), pose mapping the keyframe's camera
+        to the frame's. The trajectory does not use them."""
         import torch
         from . import Batch, BaWindow, BundleAdjuster
         if chunk < 2 or n_fixed < 1:
@@ -265,6 +272,7 @@ class SequenceFrontend:
         self.next_frame = 0
         self.loop = None
         self.loop_candidates: List[Tuple[int, int, float]] = []
+        self.loop_closures: List[Tuple[int, int, np.ndarray, int]] = []
         if loop is not None:
             self.loop = dict(loop)
             self.loop.setdefault("every", 1)
@@ -391,21 +399,36 @@ class SequenceFrontend:
         d_score = torch.empty((len(ks), 16), dtype=torch.float64, device=self._loop_dev)
         d_count = torch.empty(len(ks), dtype=torch.int32, device=self._loop_dev)
         idx.candidates_copy(len(ks), d_entry.data_ptr(), d_score.data_ptr(), 0, d_count.data_ptr())
+        d_res = None
+        ver = lp.get("verify")
+        if ver is not None:
+            # the candidates against the stored keyframes, from the rows as they lie on the device; then this chunk's
+            # frames become keyframes themselves (entry e of the store is entry e of the index)
+            ver.verify_batch(self.batch, slots, d_entry.data_ptr(), d_count.data_ptr(), lp["top_k"])
+            d_res = torch.empty(len(ks) * lp["top_k"] * LOOP_RESULT_DTYPE.itemsize, dtype=torch.uint8,
+                                device=self._loop_dev)
+            ver.results_copy(len(ks) * lp["top_k"], d_res.data_ptr())
         idx.add_batch(self.batch, slots, frames)
-        self._loop_pending.append((frames, d_entry, d_score, d_count))
+        if ver is not None:
+            ver.add_batch(self.batch, slots, [2 * k + 1 for k in ks], frames)  # pair 2 k + 1: L_k -> R_k
+        self._loop_pending.append((frames, d_entry, d_score, d_count, d_res))
 
     def _loop_collect(self) -> None:
         """The pending chunks' candidate lists into loop_candidates (waits for the context stream)."""
         if self.loop is None or not self._loop_pending:
             return
         self.ctx.sync()
-        ef, lo = self.loop["index"].entry_frames, self.loop["min_score"]
-        for frames, d_entry, d_score, d_count in self._loop_pending:
+        ef, lo, top_k = self.loop["index"].entry_frames, self.loop["min_score"], self.loop["top_k"]
+        for frames, d_entry, d_score, d_count, d_res in self._loop_pending:
             e, sc, cnt = d_entry.cpu().numpy(), d_score.cpu().numpy(), d_count.cpu().numpy()
+            res = None if d_res is None else d_res.cpu().numpy().view(LOOP_RESULT_DTYPE).reshape(len(frames), top_k)
             for q, f in enumerate(frames):
                 for k in range(int(cnt[q])):
                     if sc[q, k] >= lo:
                         self.loop_candidates.append((f, ef[int(e[q, k])], float(sc[q, k])))
+                        if res is not None and k < top_k and res[q, k]["verified"]:
+                            self.loop_closures.append((f, ef[int(e[q, k])], res[q, k]["pose"].copy(),
+                                                       int(res[q, k]["lm_inliers"])))
         self._loop_pending = []
 
     def flush(self, seconds: Dict[str, float] = None) -> None:
